@@ -8,8 +8,8 @@ S-parameter read-out) over one batch of sweep points whose permittivity grids ar
 
     python bench.py                                  # 1 GPU, 128-lambda sweep, the driver's BENCH line
     python bench.py --gpus 8                         # spawns 8 ranks itself (torch.distributed.run, RCCL); weak scaling: 128
-                                                     # points per GPU, PLUS the strong-scaling leg north_star asks for (the SAME
-                                                     # 128-lambda sweep split 8 ways) reported under "strong_scaling"
+                                                     # points per GPU; with --full PLUS the strong-scaling leg north_star asks for
+                                                     # (the SAME 128-lambda sweep split 8 ways) reported under "strong_scaling"
     python bench.py --gpus 8 --scaling strong        # only the split sweep (value = its throughput)
     python bench.py --gpus 8 --config 4              # configs[3]: 16x16x16 (Wx,Wy,lambda) sweep = 4096 solves, sharded (strong)
     python bench.py --config 3                       # configs[2]: 4 patterned layers, order [21,21], 64-lambda sweep (4 layer-solves per point)
@@ -19,9 +19,14 @@ Under `python -m torch.distributed.run ... bench.py --gpus N ...` (the driver's 
 is spawned.  No data-path collective exists: every rank solves its own contiguous block of the flattened sweep
 (torcwa_amd.sweep.shard_range); the only communication is one all_gather of the S-parameters at the end.
 
-Prints ONE JSON line on rank 0 (driver contract) with `roofline` (live HIP-event timing of the dominant kernels + the
-per-layer-solve T_roof/T_measured of SURVEY.md 8(d)) and, at N = 1, `cpu_baseline` (the oracle port of the reference's CPU
-path timed on the host cores).
+Prints ONE JSON line on rank 0 (driver contract).  A plain run sets up, warms up, times the --steps steps and prints the headline
+(`value`, `ms_per_step`, ...); `--dump-outputs DIR` writes what the last timed step computed as DIR/<name>.npy.  Everything
+else moves behind `--full`:
+
+    python bench.py --full                           # + `roofline` (live HIP-event timing of the dominant kernels, instrumented
+                                                     # timed region, + the per-layer-solve T_roof/T_measured of SURVEY.md 8(d)),
+                                                     # at N = 1 `cpu_baseline` / `parity_sample` (the oracle port of the
+                                                     # reference's CPU path timed on the host cores), at N > 1 the strong leg
 """
 import argparse
 import glob
@@ -68,12 +73,19 @@ def parse_args(argv=None):
     ap.add_argument("--streams", type=int, default=1, help="HIP streams (host threads) the chunks of a step are dealt to")
     ap.add_argument("--precision", default="high", choices=["high", "native"])
     ap.add_argument("--eig-route", default="auto", choices=["auto", "mixed", "fp64"], help="eigensolver route of the sweep drivers (torcwa_amd.sweep.solve_stack_sweep)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-strong-leg", action="store_true", help="N > 1, weak scaling: skip the additional strong-scaling measurement")
-    ap.add_argument("--cpu-points", type=int, default=3, help="sweep points the CPU baseline times (>= 1)")
-    ap.add_argument("--cpu-threads", type=int, default=0)
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: live roofline of an instrumented timed region (+ the committed profiles' figures), the CPU baseline "
+                         "and parity sample (N = 1, config 2), the strong-scaling leg (N > 1, weak, config 2)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (as the caller receives it, gathered over the ranks) to DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
+    ap.add_argument("--no-strong-leg", action="store_true", help="--full, N > 1, weak scaling: skip the additional strong-scaling measurement")
+    ap.add_argument("--cpu-points", type=int, default=3, help="--full: sweep points the CPU baseline times (>= 1)")
+    ap.add_argument("--cpu-threads", type=int, default=0, help="--full: threads of the CPU baseline; 0 = the physical cores this process may use")
     ap.add_argument("--host-profile", action="store_true", help="cProfile of one extra (untimed) step, top entries to stderr")
     args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     if args.order <= 0:
         args.order = {2: 15, 3: 21, 4: 15, 5: 25}[args.config]
     if args.batch <= 0:
@@ -156,6 +168,7 @@ def make_inputs_topopt(device):
 
 TOPOPT_EPS = 12.011610263133004 + 0.525912014756j
 _grad_norm = [None]
+_grad = [None]                 # d fom / d density of the last config-5 step (--dump-outputs)
 
 
 def run_step_topopt(rho0, order, engine):
@@ -171,6 +184,7 @@ def run_step_topopt(rho0, order, engine):
     t = [sim.S_parameters(orders=[1, 0], direction='forward', port='transmission', polarization=p, ref_order=[0, 0]) for p in ('xx', 'yx', 'xy', 'yy')]
     fom = sum(torch.abs(v) ** 2 for v in t).sum()
     fom.backward()
+    _grad[0] = rho.grad.detach()
     _grad_norm[0] = float(rho.grad.norm())
     return fom.detach().to(torch.complex128).reshape(1, 1)
 
@@ -199,6 +213,28 @@ def run_step(freq, grids, order, engine, args, chunk):
                                     precision=args.precision, engine=engine, chunk=chunk, streams=args.streams, check_info=False, eig_route=args.eig_route)
 
 
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(dirname, config, full):
+    """--dump-outputs: the result of the last timed step as the caller of the timed path receives it, as float arrays in DIR/<name>.npy.
+    configs 2 - 4: the S-parameter [points, orders, 2] (real, imaginary; float32 for complex64, float64 for complex128 results); larger than
+    DUMP_MAX_BYTES: a fixed, seeded sample of the points, in sweep order, their indices in txx_points.npy.  config 5: the figure of merit of
+    every replica and the gradient with respect to the density of rank 0's replica, float64."""
+    os.makedirs(dirname, exist_ok=True)
+    if config == 5:
+        arrays = {"fom": full.real.to(torch.float64).cpu().numpy(), "grad_density": _grad[0].to(torch.float64).cpu().numpy()}
+    else:
+        txx = torch.view_as_real(full.resolve_conj()).cpu().numpy()
+        arrays = {"txx": txx}
+        if txx.nbytes > DUMP_MAX_BYTES:
+            keep = DUMP_MAX_BYTES // (2 * (txx.nbytes // txx.shape[0]))
+            rows = np.sort(np.random.default_rng(0).choice(txx.shape[0], size=keep, replace=False))
+            arrays = {"txx": txx[rows], "txx_points": rows.astype(np.float64)}
+    for name, a in arrays.items():
+        np.save(os.path.join(dirname, name + ".npy"), np.ascontiguousarray(a))
+
+
 # ---------------------------------------------------------------------------------------------------------------------------
 # CPU baseline (oracle port of the reference, test infrastructure -- only this leg imports it)
 # ---------------------------------------------------------------------------------------------------------------------------
@@ -221,6 +257,18 @@ def host_cpu():
         pass
     logical = os.cpu_count() or 1
     return model, (len(cores) if cores else max(1, logical // 2)), logical
+
+
+def baseline_threads(phys):
+    """Threads of the CPU baseline: the physical cores, but no more than the CPUs this process may run on (affinity mask) and OMP_NUM_THREADS
+    when it is set -- a pool sized by the whole machine on a share of it oversubscribes the share."""
+    n = phys
+    if hasattr(os, "sched_getaffinity"):
+        n = min(n, len(os.sched_getaffinity(0)))
+    omp = os.environ.get("OMP_NUM_THREADS", "")
+    if omp.isdigit() and int(omp) > 0:
+        n = min(n, int(omp))
+    return max(1, n)
 
 
 def cpu_baseline(order, grid, lams, eps_sis, threads):
@@ -593,8 +641,10 @@ def main():
         from torcwa_amd.sweep import shard_indices
         return shard_indices(total, rank, world, cyclic=cyclic)
 
-    def measure(idx, steps, warmup, profile):
-        """W untimed + K timed steps over this rank's sweep points `idx`; returns (elapsed max over ranks, last result, inputs)."""
+    def measure(idx, steps, warmup, primary):
+        """W untimed + K timed steps over this rank's sweep points `idx`; returns (elapsed max over ranks, last result, inputs).  The primary
+        measurement records the HBM statistics of its timed region, and with --full its libtrx / phase instrumentation for the roofline."""
+        profile = primary and args.full
         if args.config == 3:
             freq, grids, lam, eps_si = make_inputs_stack(idx, args.batch, args.grid, device)
         elif args.config == 5:
@@ -635,15 +685,16 @@ def main():
             engine.lib.prof_enable(0 if os.environ.get("TRX_BENCH_NOPROF") == "1" else 1)
             engine.phase_report()                                                       # drop the warm-up's brackets
             engine.profile_phases = os.environ.get("TRX_BENCH_NOPROF") != "1"
-            if not EMU:
-                mstat["timed0"] = torch.cuda.memory_stats(device)
+        if primary and not EMU:
+            mstat["timed0"] = torch.cuda.memory_stats(device)
         t0 = time.perf_counter()
         for _ in range(steps):
             out = run_step(freq, grids, order, engine, args, chunk)
         barrier()
         elapsed = time.perf_counter() - t0
-        engine.lib.prof_enable(0)
-        engine.profile_phases = False
+        if profile:
+            engine.lib.prof_enable(0)
+            engine.profile_phases = False
         if world > 1:
             t = torch.tensor([elapsed], dtype=torch.float64, device=device)
             dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -661,12 +712,12 @@ def main():
             total, idx = args.points * world, np.arange(rank * args.points, (rank + 1) * args.points)
     mstat = {}
     ms0 = torch.cuda.memory_stats(device) if not EMU else {}
-    elapsed, out, (freq, grids, lam, eps_si, chunk) = measure(idx, args.steps, args.warmup, profile=True)
+    elapsed, out, (freq, grids, lam, eps_si, chunk) = measure(idx, args.steps, args.warmup, primary=True)
     ms1 = torch.cuda.memory_stats(device) if not EMU else {}
     n_fail = engine.failures()
     if n_fail:
         raise SystemExit(f"bench invalid: {n_fail} numerical failures (info != 0) inside the timed region")
-    roof = roofline(engine, args, elapsed, args.steps, n, len(idx) * layers_per_point, chunk) if rank == 0 else None
+    roof = roofline(engine, args, elapsed, args.steps, n, len(idx) * layers_per_point, chunk) if rank == 0 and args.full else None
     if args.host_profile and rank == 0:
         import cProfile
         import pstats
@@ -678,12 +729,14 @@ def main():
         pstats.Stats(pr, stream=sys.stderr).sort_stats("tottime").print_stats(25)
     full = gather_sweep(out, total, cyclic=cyclic and scaling != "weak") if world > 1 else out      # the one collective of the job (RCCL all_gather, KB-sized)
     value = total * layers_per_point * args.steps / elapsed
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, args.config, full)
 
     # ---- strong-scaling leg (north_star: ">= 6x strong scaling of a wavelength sweep at 8 GPUs") ------------------------------
     strong = None
-    if world > 1 and scaling == "weak" and args.config == 2 and not args.no_strong_leg:
+    if args.full and world > 1 and scaling == "weak" and args.config == 2 and not args.no_strong_leg:
         sidx = local_block(args.batch)
-        el_s, out_s, _ = measure(sidx, args.steps, 1, profile=False)
+        el_s, out_s, _ = measure(sidx, args.steps, 1, primary=False)
         full_s = gather_sweep(out_s, args.batch)
         n_fail = engine.failures()
         strong = {"workload": "the SAME %d-lambda sweep split over %d GPUs (%d-%d points per GPU)" % (args.batch, world, args.batch // world, -(-args.batch // world)),
@@ -734,14 +787,17 @@ def main():
             res["fom"], res["grad_norm"] = float(full[0, 0].real), _grad_norm[0]
         if strong is not None:
             res["strong_scaling"] = strong
-        res["roofline"] = roof
+        if args.full:
+            res["roofline"] = roof
         if EMU:
             # the CPU kernel-logic emulator is a launcher-plumbing test: it must never look like a measurement
             res["emulator_plumbing"] = {"units_per_s": res["value"], "ms_per_step": res["ms_per_step"]}
-            res["value"], res["ms_per_step"], res["roofline"] = None, None, None
-        if not args.no_cpu_baseline and world == 1 and args.config == 2:
+            res["value"], res["ms_per_step"] = None, None
+            if args.full:
+                res["roofline"] = None
+        if args.full and not args.no_cpu_baseline and world == 1 and args.config == 2:
             model, phys, logical = host_cpu()
-            threads = args.cpu_threads if args.cpu_threads > 0 else phys
+            threads = args.cpu_threads if args.cpu_threads > 0 else baseline_threads(phys)
             npts = max(1, min(args.cpu_points, len(lam)))
             pick = sorted(set(int(round(i * (len(lam) - 1) / max(npts - 1, 1))) for i in range(npts)))
             secs, vals, dt_flush, dt128, v128 = cpu_baseline(order, args.grid, [lam[i] for i in pick], [eps_si[i] for i in pick], threads)
@@ -757,7 +813,7 @@ def main():
                                    "cpu_model": model, "physical_cores": phys, "logical_cpus": logical,
                                    "seconds_per_layer_solve": secs, "flush_denormal_seconds_footnote": dt_flush,
                                    "sample": "%d layer-solves of the same workload (lambda = %s nm), complex64, denormals not flushed (as the reference "
-                                             "runs), oracle/rcwa_oracle.py on torch-CPU with %d threads = physical cores; footnote: the first point "
+                                             "runs), oracle/rcwa_oracle.py on torch-CPU with %d threads (physical cores this process may use); footnote: the first point "
                                              "again with torch.set_flush_denormal(True)" % (len(secs), ", ".join("%.1f" % lam[i] for i in pick), threads)}
         print(json.dumps(res), flush=True)
     if world > 1:

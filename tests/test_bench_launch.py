@@ -27,8 +27,8 @@ def _bench(*flags, gpus=1):
 
 
 def test_bench_spawns_its_own_ranks_weak_and_strong():
-    one = _bench("--batch", "3", gpus=1)
-    two = _bench("--batch", "3", gpus=2)
+    one = _bench("--batch", "3", "--full", gpus=1)
+    two = _bench("--batch", "3", "--full", gpus=2)
     assert one["n_gpus"] == 1 and two["n_gpus"] == 2 and two["config"]["backend"] == "gloo"
     assert one["scaling"] == "weak" and two["scaling"] == "weak"
     assert one["gathered_points"] == 3 and two["gathered_points"] == 6          # weak: 3 points per rank
@@ -66,3 +66,24 @@ def test_bench_config3_stack_and_config5_adjoint():
     assert "configs[4]" in one["config"]["workload"] and one["dtype"] == "c128" and one["gathered_points"] == 1 and two["gathered_points"] == 2
     assert one["fom"] > 0 and one["grad_norm"] > 0 and np.isclose(one["fom"], two["fom"], rtol=1e-9)
     assert "forward + adjoint" in one["metric"]
+
+
+def test_bench_plain_line_and_dump_outputs(tmp_path):
+    """A plain run carries the headline only (no roofline, CPU baseline or strong leg: those are --full); --dump-outputs writes the
+    gathered result of the last timed step, identical from run to run, and the same as the --full run's."""
+    a, b, f = tmp_path / "a", tmp_path / "b", tmp_path / "f"
+    two = _bench("--batch", "3", "--steps", "2", "--dump-outputs", str(a), gpus=2)
+    for key in ("roofline", "strong_scaling", "cpu_baseline", "parity_sample"):
+        assert key not in two
+    assert two["steps"] == 2 and two["emulator_plumbing"]["ms_per_step"] > 0
+    _bench("--batch", "3", "--steps", "2", "--dump-outputs", str(b), gpus=2)
+    _bench("--batch", "3", "--full", "--dump-outputs", str(f), gpus=2)
+    txx = np.load(a / "txx.npy")
+    assert txx.shape == (6, 1, 2) and txx.dtype in (np.float32, np.float64)
+    assert np.array_equal(txx, np.load(b / "txx.npy")) and np.array_equal(txx, np.load(f / "txx.npy"))
+    assert np.allclose(txx[0, 0], two["txx00_sample"], rtol=1e-6)
+    c5 = tmp_path / "c5"
+    one = _bench("--config", "5", "--dump-outputs", str(c5))
+    fom, grad = np.load(c5 / "fom.npy"), np.load(c5 / "grad_density.npy")
+    assert fom.dtype == np.float64 and np.isclose(fom.reshape(-1)[0], one["fom"], rtol=1e-12)
+    assert grad.shape == (700, 300) and np.isclose(np.linalg.norm(grad), one["grad_norm"], rtol=1e-9)
