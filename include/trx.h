@@ -51,6 +51,21 @@ size_t trx_convmat_ws_bytes(int dtype, int batch, int nx, int ny, int ox, int oy
 int trx_convmat(int dtype, int grid_is_complex, const void* grid, int batch, int nx, int ny, int ox, int oy,
                 void* out, void* ws, size_t ws_bytes, void* stream);
 
+/* ---- Fourier factorisation, Li's inverse rule (no reference counterpart: the reference has Laurent's rule only) ---------------------
+ * L. Li, JOSA A 13, 1870 (1996); 14, 2758 (1997).  For each grid[b] ([nx, ny], layout and index map as trx_convmat):
+ *   Ex[(m,n),(m',n')] = F[m,m',n-n'],  F[m,m',q] = (1/ny) sum_y Uy[y][m,m'] e^{-2 pi i q y/ny},  Uy[y] = Toeplitz_x(1/grid[:,y])^-1
+ *   Ey[(m,n),(m',n')] = G[n,n',m-m'],  G[n,n',p] = (1/nx) sum_x Ux[x][n,n'] e^{-2 pi i p x/nx},  Ux[x] = Toeplitz_y(1/grid[x,:])^-1
+ * where Toeplitz_x(f)[m,m'] = fhat[m-m'] of the 1-D DFT along x divided by nx ((2ox+1)^2), Toeplitz_y likewise ((2oy+1)^2).  Ex multiplies the
+ * x component of E (inverse rule across the x discontinuities), Ey the y component.  Ex, Ey: [batch,N,N] outputs in `dtype`.
+ * Ux [batch,nx,2oy+1,2oy+1], Uy [batch,ny,2ox+1,2ox+1]: optional complex128 outputs of the small inverses (NULL: not kept; the adjoint needs
+ * them).  info[batch] (device): 0 ok, 1 a grid value is zero, 2 a Toeplitz block is singular.  All arithmetic is fp64 for both dtypes.
+ * Requires nx > 2ox, ny > 2oy and max(nx, ny) <= 2048 (as trx_convmat); 2*max(ox,oy)+1 <= 99, i.e. max(ox,oy) <= 49 (one Toeplitz block of
+ * (2o+1)^2 complex128 elements is held in the LDS of one CU, 160 KiB on gfx950), else TRX_ERR_UNSUPPORTED.  The workspace holds the pruned
+ * DFTs of 1/grid, the per-direction transforms and, unless Ux / Uy are given, the inverses of a chunk of rows no larger than one output. */
+size_t trx_convmat_li_ws_bytes(int dtype, int batch, int nx, int ny, int ox, int oy);
+int trx_convmat_li(int dtype, int grid_is_complex, const void* grid, int batch, int nx, int ny, int ox, int oy, void* Ex, void* Ey,
+                   void* Ux, void* Uy, int* info, void* ws, size_t ws_bytes, void* stream);
+
 /* ---- dense complex building blocks (the torch.matmul / torch.linalg.inv call sites, rcwa.py:1157-1304) -------- */
 /* C = alpha*op(A)*op(B) + beta*C, batched with element strides; alpha/beta point to HOST complex scalars. */
 int trx_gemm(int dtype, int opA, int opB, int m, int n, int k, const void* alpha, const void* A, int lda,
@@ -200,6 +215,17 @@ int trx_redheffer_halfspace(int dtype, int side, const void* bd, const void* con
 size_t trx_build_a_ws_bytes(int dtype, int N, int batch);
 int trx_build_a(int dtype, const void* E, const void* Einv, const void* mu, const void* kx, const void* ky, int N, int batch, void* A,
                 void* ws, size_t ws_bytes, void* stream);
+
+/* P, Q (as trx_build_pq) with a convolution matrix per field component (Li's rule; later also diagonal-anisotropic inputs):
+ *   P = [[Kx Ei Ky, My - Kx Ei Kx],[Ky Ei Ky - Mx, -Ky Ei Kx]],  Q = [[-Kx Mi Ky, Kx Mi Kx - Ey],[Ex - Ky Mi Ky, Ky Mi Kx]]
+ * Einv / Minv: inverses of the LAURENT matrices (they act on Ez / Hz).  Ex = Ey = E, Mx = My = M gives trx_build_pq. */
+int trx_build_pq_aniso(int dtype, const void* Ex, const void* Ey, const void* Einv, const void* Mx, const void* My, const void* Minv,
+                       const void* kx, const void* ky, int N, int batch, void* P, void* Q, void* stream);
+/* A = P Q for homogeneous mu[batch] with per-component Ex, Ey (two N^3 GEMMs, as trx_build_a):
+ *   A = [[mu Ex - Ky^2 - Kx Gx, KxKy - Kx Gy],[KxKy - Ky Gx, mu Ey - Kx^2 - Ky Gy]],  Gx = Einv (Kx Ex), Gy = Einv (Ky Ey). */
+size_t trx_build_a_aniso_ws_bytes(int dtype, int N, int batch);
+int trx_build_a_aniso(int dtype, const void* Ex, const void* Ey, const void* Einv, const void* mu, const void* kx, const void* ky, int N, int batch,
+                      void* A, void* ws, size_t ws_bytes, void* stream);
 
 /* ---- measurement aid (no reference counterpart): HIP-event timing of the dominant kernels --------------------
  * trx_prof_enable(1) makes the instrumented launch sites record hipEvents on the launch stream.  Sampling is systematic and

@@ -19,6 +19,14 @@ _SIGS = {
     "trx_strerror": (c_char_p, [c_int]),
     "trx_convmat_ws_bytes": (c_size_t, [c_int, c_int, c_int, c_int, c_int, c_int]),
     "trx_convmat": (c_int, [c_int, c_int, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "trx_convmat_li_ws_bytes": (c_size_t, [c_int, c_int, c_int, c_int, c_int, c_int]),
+    "trx_convmat_li": (c_int, [c_int, c_int, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                               c_void_p, c_size_t, c_void_p]),
+    "trx_build_pq_aniso": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p,
+                                   c_void_p, c_void_p]),
+    "trx_build_a_aniso_ws_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "trx_build_a_aniso": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_size_t,
+                                  c_void_p]),
     "trx_gemm": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_long, c_void_p, c_int, c_long,
                          c_void_p, c_void_p, c_int, c_long, c_int, c_void_p]),
     "trx_lu_solve": (c_int, [c_int, c_void_p, c_int, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p]),

@@ -45,6 +45,71 @@ class ConvMatFn(torch.autograd.Function):
         return g.to(gdt), None, None, None, None
 
 
+def _twiddle(n, o, dev):
+    """[n, 4o+1] complex128: exp(+2 pi i (q-2o) r / n) with exact integer phase reduction (the conjugate of the forward twiddle)."""
+    r = torch.arange(n, device=dev, dtype=torch.int64)[:, None]
+    q = torch.arange(-2 * o, 2 * o + 1, device=dev, dtype=torch.int64)[None, :]
+    return torch.exp(2j * math.pi * ((r * q) % n).to(torch.float64) / n)
+
+
+def _diag_index(w, o, dev):
+    """Flattened (a, a') of a w x w block -> a - a' + 2o (w = 2o+1): the Toeplitz diagonal of each entry."""
+    a = torch.arange(w, device=dev)
+    return (a[:, None] - a[None, :] + 2 * o).reshape(-1)
+
+
+class ConvMatLiFn(torch.autograd.Function):
+    """(Ex, Ey) = Li's inverse-rule convolution matrices of a grid (include/trx.h: trx_convmat_li).  The backward is the adjoint chain of
+    the forward: scatter (index_add), inverse transform along the other axis, gT = -U^H gU U^H per Toeplitz block (batched trx_gemm),
+    Toeplitz-diagonal sums, inverse pruned DFT, and the derivative of 1/g (times conj(-1/g^2); the real part for a real grid)."""
+
+    @staticmethod
+    def forward(ctx, grid, ox, oy, cdtype, engine):
+        Ex, Ey, Ux, Uy = engine.convmat_li(grid, ox, oy, cdtype, keep_inverses=True)
+        ctx.meta = (ox, oy, grid.is_complex(), grid.dtype)
+        ctx.engine = engine
+        ctx.save_for_backward(grid, Ux, Uy)
+        return Ex, Ey
+
+    @staticmethod
+    def _block_grad(eng, gF, U, tw):
+        """gF [B, w^2, nq2] (adjoint of the scatter), U [B, R, w, w], tw [R, nq2] conjugate twiddles -> gT [B, R, w, w]."""
+        B, R, w, _ = U.shape
+        gU = (tw[None] @ gF.transpose(1, 2)).reshape(B * R, w, w).contiguous() / R      # [B, R, w^2] adjoint of the transform
+        Uf = U.reshape(B * R, w, w)
+        gT = -eng.gemm(eng.gemm(Uf, gU, opA=2), Uf, opB=2)                                  # -U^H gU U^H
+        return gT.reshape(B, R, w * w)
+
+    @staticmethod
+    def backward(ctx, gEx, gEy):
+        ox, oy, cplx, gdt = ctx.meta
+        grid, Ux, Uy = ctx.saved_tensors
+        eng = ctx.engine
+        B, nx, ny = grid.shape
+        dev, z = grid.device, torch.complex128
+        wx, wy = 2 * ox + 1, 2 * oy + 1
+        np_, nq = 4 * ox + 1, 4 * oy + 1
+        ix, iy = _diag_index(wx, ox, dev), _diag_index(wy, oy, dev)
+        gr = torch.zeros((B, nx, ny), dtype=z, device=dev)
+        if gEx is not None:                      # Ex[(m,n),(m',n')] = F[m,m',n-n'],  F = transform along y of Uy
+            g = gEx.to(z).reshape(B, wx, wy, wx, wy).permute(0, 1, 3, 2, 4).reshape(B, wx * wx, wy * wy)
+            gF = torch.zeros((B, wx * wx, nq), dtype=z, device=dev).index_add_(2, iy, g)
+            gT = ConvMatLiFn._block_grad(eng, gF, Uy, _twiddle(ny, oy, dev))             # [B, ny, wx^2]
+            ga = torch.zeros((B, ny, np_), dtype=z, device=dev).index_add_(2, ix, gT)      # Toeplitz-diagonal sums
+            gr += (_twiddle(nx, ox, dev)[None] @ ga.transpose(1, 2)) / nx                 # inverse pruned DFT along x
+        if gEy is not None:                      # Ey[(m,n),(m',n')] = G[n,n',m-m'],  G = transform along x of Ux
+            g = gEy.to(z).reshape(B, wx, wy, wx, wy).permute(0, 2, 4, 1, 3).reshape(B, wy * wy, wx * wx)
+            gG = torch.zeros((B, wy * wy, np_), dtype=z, device=dev).index_add_(2, ix, g)
+            gT = ConvMatLiFn._block_grad(eng, gG, Ux, _twiddle(nx, ox, dev))             # [B, nx, wy^2]
+            ga = torch.zeros((B, nx, nq), dtype=z, device=dev).index_add_(2, iy, gT)
+            gr += (ga @ _twiddle(ny, oy, dev).transpose(0, 1)[None]) / ny                 # inverse pruned DFT along y
+        r = 1 / grid.to(z)
+        gg = torch.conj(-r * r) * gr                                                       # d(1/g)/dg = -1/g^2 (holomorphic)
+        if not cplx:
+            gg = torch.real(gg)
+        return gg.to(gdt), None, None, None, None
+
+
 class GemmFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, A, B, engine):

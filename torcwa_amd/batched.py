@@ -71,7 +71,12 @@ def _halfspace_V(kx, ky, epsmu):
 class BatchedRCWA:
     def __init__(self, freq, order, L, *, batch=None, dtype=torch.complex64, device=None, stable_eig_grad=True,
                  avoid_Pinv_instability=False, max_Pinv_instability=0.005, precision="high", engine=None,
-                 keep_coupling=True, fold_layers=False, eig_route="auto", route_hint=None):
+                 keep_coupling=True, fold_layers=False, eig_route="auto", route_hint=None, fourier_rule="laurent"):
+        if fourier_rule not in ("laurent", "li"):
+            raise ValueError(f"fourier_rule must be 'laurent' or 'li', got {fourier_rule!r}")
+        # fourier_rule="li": Li's inverse rule for the x / y components of D in every patterned layer (Ex, Ey convolution matrices,
+        # include/trx.h trx_convmat_li); Ez / Hz keep Laurent's matrices (E^-1 in P, trx_hmodes, eps_conv).  "laurent": the reference's rule.
+        self.fourier_rule = fourier_rule
         if dtype != torch.complex64 and dtype != torch.complex128:                      # rcwa.py:37-41
             warnings.warn("Invalid simulation data type. Set as torch.complex64.", UserWarning)
             dtype = torch.complex64
@@ -116,6 +121,7 @@ class BatchedRCWA:
         self.layer_N = 0
         self.thickness = []
         self.eps_conv, self.mu_conv = [], []
+        self.eps_conv_x, self.eps_conv_y = [], []      # fourier_rule="li" with keep_coupling: Ex, Ey per layer (None: homogeneous / folded)
         self.P, self.Q = [], []
         self.kz_norm, self.E_eigvec, self.H_eigvec = [], [], []
         self.Cplus, self.Cminus = [], []
@@ -202,6 +208,17 @@ class BatchedRCWA:
             C = eng.convmat(g.contiguous(), self.order[0], self.order[1], cdt)          # rcwa.py:1183-1204
             return C, None, None
 
+        def conv_li(v, homog, C):
+            """Li's (Cx, Cy) of a patterned grid; a homogeneous layer has Cx = Cy = C (the scaled identity)."""
+            if homog:
+                return C, C
+            g = torch.as_tensor(v, device=self._device)
+            if g.dim() == 2:
+                g = g[None].expand(B, -1, -1)
+            if diff:
+                return ag.ConvMatLiFn.apply(g.contiguous(), self.order[0], self.order[1], cdt, eng)
+            return eng.convmat_li(g.contiguous(), self.order[0], self.order[1], cdt)[:2]
+
         if eps_h and mu_h and not diff and not self.keep_coupling:
             self._add_homogeneous_layer_bd(thickness, self._bvec(eps), self._bvec(mu))
             self._fold_last_layer()
@@ -215,8 +232,14 @@ class BatchedRCWA:
             M, Minv, mu_s = None, None, self._bvec(mu)
         else:
             M, Minv, mu_s = conv(mu, mu_h)
+        li = self.fourier_rule == "li" and not (eps_h and mu_h)
+        Ex, Ey = conv_li(eps, eps_h, E) if li else (None, None)
+        Mx, My = conv_li(mu, mu_h, M) if (li and M is not None) else (None, None)
         self.eps_conv.append(E)
         self.mu_conv.append(M)
+        keep_li = li and self.keep_coupling and not eps_h
+        self.eps_conv_x.append(Ex if keep_li else None)
+        self.eps_conv_y.append(Ey if keep_li else None)
         self.layer_N += 1
         d = self._bvec(thickness, self._rdtype)
         self.thickness.append(d)
@@ -227,9 +250,11 @@ class BatchedRCWA:
         if Minv is None and M is not None:
             Minv = inv(M)
         if diff:
-            P, Q = self._pq_torch(E, Einv, M, Minv, kxd, kyd)
+            P, Q = self._pq_torch(E, Einv, M, Minv, kxd, kyd, Ex, Ey, Mx, My)
         elif lean:
             P = Q = None
+        elif li:
+            P, Q = eng.build_pq_aniso(Ex, Ey, Einv, Mx, My, Minv, kxd, kyd)
         else:
             P, Q = eng.build_pq(E, Einv, M, Minv, kxd, kyd)
         if eps_h and mu_h:                                                              # rcwa.py:1206-1222
@@ -246,8 +271,11 @@ class BatchedRCWA:
                 lam, W = Eig.apply(A) if self.stable_eig_grad else Eig.apply(A, Eig.UNBROADENED)
             else:
                 # A = P Q (rcwa.py:1236): with homogeneous mu the block structure needs two N^3 products, not one (2N)^3
-                A = eng.build_a(E, Einv, mu_s, kxd, kyd) if mu_h else eng.gemm(P, Q)
-                del Einv
+                if li:
+                    A = eng.build_a_aniso(Ex, Ey, Einv, mu_s, kxd, kyd) if mu_h else eng.gemm(P, Q)
+                else:
+                    A = eng.build_a(E, Einv, mu_s, kxd, kyd) if mu_h else eng.gemm(P, Q)
+                del Einv, Ex, Ey, Mx, My          # Li's matrices live on only in eps_conv_x / eps_conv_y (keep_coupling)
                 # mixed-precision eigensolver: two Newton steps for a complex64 problem (1e-5 gate), three for complex128 (engine.eig)
                 lam, W = self._eig_call(A, refine_steps=3 if self._dtype == torch.complex128 else 2)      # torch_eig.py:14
                 del A
@@ -279,6 +307,7 @@ class BatchedRCWA:
             self._running, _ = self._star(self._running, S, [[], []], [[], []])
         self.layer_S11[i] = self.layer_S21[i] = None
         self.eps_conv[i] = None
+        self.eps_conv_x[i] = self.eps_conv_y[i] = None
         self._n_folded = i + 1
 
     def _add_homogeneous_layer_bd(self, thickness, eps_s, mu_s):
@@ -304,17 +333,21 @@ class BatchedRCWA:
         self.layer_N += 1
         self.thickness.append(d)
         self.kz_norm.append(torch.cat((kz, kz), dim=1))
-        for lst in (self.eps_conv, self.mu_conv, self.P, self.Q, self.E_eigvec, self.H_eigvec, self.Cplus, self.Cminus):
+        for lst in (self.eps_conv, self.mu_conv, self.eps_conv_x, self.eps_conv_y, self.P, self.Q, self.E_eigvec, self.H_eigvec, self.Cplus,
+                    self.Cminus):
             lst.append(None)
 
     @staticmethod
-    def _pq_torch(E, Ei, M, Mi, kx, ky):
-        """P, Q (rcwa.py:1226-1232) with broadcasting instead of dense diagonal products (differentiable)."""
+    def _pq_torch(E, Ei, M, Mi, kx, ky, Ex=None, Ey=None, Mx=None, My=None):
+        """P, Q (rcwa.py:1226-1232) with broadcasting instead of dense diagonal products (differentiable).  Ex, Ey, Mx, My: Li's
+        per-component matrices (default: the Laurent E, M in both places)."""
+        Ex, Ey = (E, E) if Ex is None else (Ex, Ey)
+        Mx, My = (M, M) if Mx is None else (Mx, My)
         kxi, kyi, kxj, kyj = kx[:, :, None], ky[:, :, None], kx[:, None, :], ky[:, None, :]
-        P = torch.cat((torch.cat((kxi * Ei * kyj, M - kxi * Ei * kxj), dim=2),
-                       torch.cat((kyi * Ei * kyj - M, -(kyi * Ei * kxj)), dim=2)), dim=1)
-        Q = torch.cat((torch.cat((-(kxi * Mi * kyj), kxi * Mi * kxj - E), dim=2),
-                       torch.cat((E - kyi * Mi * kyj, kyi * Mi * kxj), dim=2)), dim=1)
+        P = torch.cat((torch.cat((kxi * Ei * kyj, My - kxi * Ei * kxj), dim=2),
+                       torch.cat((kyi * Ei * kyj - Mx, -(kyi * Ei * kxj)), dim=2)), dim=1)
+        Q = torch.cat((torch.cat((-(kxi * Mi * kyj), kxi * Mi * kxj - Ey), dim=2),
+                       torch.cat((Ex - kyi * Mi * kyj, kyi * Mi * kxj), dim=2)), dim=1)
         return P, Q
 
     def _solve_layer_smatrix_diff(self):

@@ -3,7 +3,7 @@
 
 using namespace trx;
 
-extern "C" int trx_version(void) { return 100; }   // 0.1.0
+extern "C" int trx_version(void) { return 200; }   // 0.2.0: trx_convmat_li, trx_build_pq_aniso, trx_build_a_aniso
 
 extern "C" const char* trx_strerror(int code) {
     switch (code) {

@@ -135,6 +135,30 @@ class Engine:
                                         ws.data_ptr(), nws, self.stream))
         return out
 
+    @_phase("assembly (convolution matrices, E^-1, A = PQ)")
+    def convmat_li(self, grid, ox, oy, dtype, keep_inverses=False):
+        """[B,nx,ny] grid -> (Ex, Ey) [B,N,N], Li's inverse-rule convolution matrices of the x and y field components (include/trx.h:
+        trx_convmat_li).  keep_inverses: also return the complex128 Toeplitz inverses Ux [B,nx,2oy+1,2oy+1], Uy [B,ny,2ox+1,2ox+1]
+        (for the adjoint); otherwise (Ex, Ey, None, None)."""
+        B, nx, ny = grid.shape
+        cplx = grid.is_complex()
+        grid = self._c(grid.to(dtype if cplx else _REAL[dtype]))
+        N = (2 * ox + 1) * (2 * oy + 1)
+        Ex = torch.empty((B, N, N), dtype=dtype, device=self.device)
+        Ey = torch.empty_like(Ex)
+        Ux = Uy = None
+        if keep_inverses:
+            Ux = torch.empty((B, nx, 2 * oy + 1, 2 * oy + 1), dtype=torch.complex128, device=self.device)
+            Uy = torch.empty((B, ny, 2 * ox + 1, 2 * ox + 1), dtype=torch.complex128, device=self.device)
+        info = self._ints(B)
+        nws = self.lib.convmat_li_ws_bytes(_CODE[dtype], B, nx, ny, ox, oy)
+        ws = self._ws(nws)
+        self.lib.check(self.lib.convmat_li(_CODE[dtype], int(cplx), grid.data_ptr(), B, nx, ny, ox, oy, Ex.data_ptr(), Ey.data_ptr(),
+                                           Ux.data_ptr() if keep_inverses else None, Uy.data_ptr() if keep_inverses else None,
+                                           info.data_ptr(), ws.data_ptr(), nws, self.stream))
+        self._info(info, "convmat_li (1: zero grid value, 2: singular Toeplitz block)")
+        return Ex, Ey, Ux, Uy
+
     # -- dense blocks ----------------------------------------------------------------------------------
     def gemm(self, A, Bm, *, opA=0, opB=0, alpha=1.0, beta=0.0, out=None):
         """Batched C = alpha op(A) op(B) + beta C for contiguous [B,*,*] operands."""
@@ -343,6 +367,31 @@ class Engine:
         ws = self._ws(nws)
         self.lib.check(self.lib.build_a(_CODE[dt], self._c(E).data_ptr(), self._c(Einv).data_ptr(), self._c(mu.to(dt)).data_ptr(), self._c(kx).data_ptr(),
                                         self._c(ky).data_ptr(), N, B, A.data_ptr(), ws.data_ptr(), nws, self.stream))
+        return A
+
+    @_phase("assembly (convolution matrices, E^-1, A = PQ)")
+    def build_pq_aniso(self, Ex, Ey, Einv, Mx, My, Minv, kx, ky):
+        """P, Q with per-component convolution matrices (Li's rule; include/trx.h: trx_build_pq_aniso)."""
+        B, N, _ = Ex.shape
+        dt = Ex.dtype
+        P = torch.empty((B, 2 * N, 2 * N), dtype=dt, device=self.device)
+        Q = torch.empty_like(P)
+        ops = [self._c(t) for t in (Ex, Ey, Einv, Mx, My, Minv, kx, ky)]
+        self._check(*ops)
+        self.lib.check(self.lib.build_pq_aniso(_CODE[dt], *[t.data_ptr() for t in ops], N, B, P.data_ptr(), Q.data_ptr(), self.stream))
+        return P, Q
+
+    @_phase("assembly (convolution matrices, E^-1, A = PQ)")
+    def build_a_aniso(self, Ex, Ey, Einv, mu, kx, ky):
+        """A = P Q for homogeneous mu [B] with per-component Ex, Ey (two N^3 GEMMs; include/trx.h: trx_build_a_aniso)."""
+        B, N, _ = Ex.shape
+        dt = Ex.dtype
+        A = torch.empty((B, 2 * N, 2 * N), dtype=dt, device=self.device)
+        nws = self.lib.build_a_aniso_ws_bytes(_CODE[dt], N, B)
+        ws = self._ws(nws)
+        ops = [self._c(t) for t in (Ex, Ey, Einv, mu.to(dt), kx, ky)]
+        self._check(*ops)
+        self.lib.check(self.lib.build_a_aniso(_CODE[dt], *[t.data_ptr() for t in ops], N, B, A.data_ptr(), ws.data_ptr(), nws, self.stream))
         return A
 
 

@@ -14,10 +14,12 @@ pi = PI_REF
 
 class rcwa(FieldMixin):
     def __init__(self, freq, order, L, *, dtype=torch.complex64, device=None, stable_eig_grad=True,
-                 avoid_Pinv_instability=False, max_Pinv_instability=0.005, precision="high", engine=None):
+                 avoid_Pinv_instability=False, max_Pinv_instability=0.005, precision="high", engine=None, fourier_rule="laurent"):
+        # fourier_rule (extension, keyword-only): "laurent" (the reference's factorisation) or "li" (Li's inverse rule for the in-plane
+        # field components of every patterned layer; faster convergence in the order for high-contrast gratings)
         self._b = BatchedRCWA(freq, order, L, batch=1, dtype=dtype, device=device, stable_eig_grad=stable_eig_grad,
                               avoid_Pinv_instability=avoid_Pinv_instability, max_Pinv_instability=max_Pinv_instability,
-                              precision=precision, engine=engine)
+                              precision=precision, engine=engine, fourier_rule=fourier_rule)
         self._dtype = self._b._dtype
         self._device = self._b._device
         self.freq = torch.as_tensor(freq, dtype=self._dtype, device=self._device)      # rcwa.py:60
@@ -138,6 +140,8 @@ class rcwa(FieldMixin):
     Vi = property(lambda self: self._u(self._b._Vi.dense()))
     Vo = property(lambda self: self._u(self._b._Vo.dense()))
     eps_conv = property(lambda self: self._ul(self._b.eps_conv))
+    eps_conv_x = property(lambda self: self._ul(self._b.eps_conv_x))
+    eps_conv_y = property(lambda self: self._ul(self._b.eps_conv_y))
     mu_conv = property(lambda self: self._ul(self._b.mu_conv))
     P = property(lambda self: self._ul(self._b.P))
     Q = property(lambda self: self._ul(self._b.Q))

@@ -77,10 +77,10 @@ def rectangle_density(nx, ny, Lx, Ly, Wx, Wy, Cx, Cy, theta=0.0, edge_sharpness=
 
 
 def _solve_chunk(freq, layers, order, L, eps_in, eps_out, inc_ang, azi_ang, dtype, precision, engine, orders,
-                 polarization, direction, port, check_info, eig_route="auto", route_hint=None):
+                 polarization, direction, port, check_info, eig_route="auto", route_hint=None, fourier_rule="laurent"):
     """layers: list of (thickness, eps[, mu]); thickness scalar or [b]; eps/mu scalar, [b] or [b,nx,ny]."""
     sim = BatchedRCWA(freq, order, L, dtype=dtype, precision=precision, engine=engine, keep_coupling=False, fold_layers=True,
-                      eig_route=eig_route, route_hint=route_hint)
+                      eig_route=eig_route, route_hint=route_hint, fourier_rule=fourier_rule)
     if eps_in is not None:
         sim.add_input_layer(eps=eps_in)
     if eps_out is not None:
@@ -96,10 +96,12 @@ def _solve_chunk(freq, layers, order, L, eps_in, eps_out, inc_ang, azi_ang, dtyp
 # allocator -- single patterned layer, order [15,15], 128 points: 75.8 GB allocated / 111.8 GB reserved = 10.0 / 14.8 matrices per point; 4-layer stack
 # with the streaming cascade, order [21,21], 64 points: 228 / 247 GB = 16.3 / 17.6.  precision="native" halves the element.
 _POINT_MATRICES = {1: 15.0, 2: 18.0}          # layers == 1 / layers >= 2 (what the allocator RESERVES, which is what must fit)
+# fourier_rule="li": Ex and Ey (two N x N = n^2 / 4 matrices each) live next to E, E^-1 and the assembly workspace until A exists
+_LI_EXTRA = 0.5
 _HEADROOM = 0.10                               # fraction of the device memory a sweep leaves free
 
 
-def auto_chunk(B, order, n_layers, precision, device, dtype=torch.complex64, streams=1):
+def auto_chunk(B, order, n_layers, precision, device, dtype=torch.complex64, streams=1, fourier_rule="laurent"):
     """Largest number of points solved in lock-step that fits the free HBM of `device` with _HEADROOM to spare (a multiple of 8 when it
     is cut: the mixed-precision eigensolver and its iteration groups want batches of at least 8).  Raises with the numbers when not even
     one point fits -- instead of an allocator error in the middle of a solve."""
@@ -109,7 +111,8 @@ def auto_chunk(B, order, n_layers, precision, device, dtype=torch.complex64, str
     # element size of the COMPUTE dtype: complex128 unless a complex64 problem is solved natively (BatchedRCWA: precision="native" only
     # halves the element of complex64 problems); `streams` chunks are resident at once when the sweep is dealt to several streams
     elem = 8 if (precision == "native" and dtype == torch.complex64) else 16
-    per_point = _POINT_MATRICES[1 if n_layers <= 1 else 2] * n * n * elem * max(1, int(streams))
+    mats = _POINT_MATRICES[1 if n_layers <= 1 else 2] + (_LI_EXTRA if fourier_rule == "li" else 0.0)
+    per_point = mats * n * n * elem * max(1, int(streams))
     free, total = torch.cuda.mem_get_info(device)
     free += torch.cuda.memory_reserved(device) - torch.cuda.memory_allocated(device)      # the caching allocator's idle blocks are ours to reuse
     budget = free - _HEADROOM * total
@@ -117,7 +120,7 @@ def auto_chunk(B, order, n_layers, precision, device, dtype=torch.complex64, str
     if fit < 1:
         raise RuntimeError("torcwa_amd sweep: one sweep point at order %s needs about %.1f GB of HBM (%d x %d complex matrices x %.0f), but only "
                            "%.1f GB are free on %s (%.1f GB total, %.0f %% kept as headroom); free memory or lower the order"
-                           % (list(order), per_point / 1e9, n, n, _POINT_MATRICES[1 if n_layers <= 1 else 2], free / 1e9, device, total / 1e9, 100 * _HEADROOM))
+                           % (list(order), per_point / 1e9, n, n, mats, free / 1e9, device, total / 1e9, 100 * _HEADROOM))
     if fit >= B:
         return B
     return fit if fit < 8 else fit - fit % 8
@@ -133,19 +136,24 @@ def _slice(v, lo, hi, B):
 
 def solve_stack_sweep(freq, layers, order, L, *, eps_in=None, eps_out=None, inc_ang=0.0, azi_ang=0.0, dtype=torch.complex64,
                       precision="high", engine=None, chunk=None, streams=1, orders=((0, 0),), polarization="xx",
-                      direction="forward", port="transmission", check_info=True, eig_route="auto"):
+                      direction="forward", port="transmission", check_info=True, eig_route="auto", fourier_rule="laurent"):
     """B sweep points of a multi-layer stack (BASELINE.json configs 2-4): the reference's per-point Python loop
     (example/Example1-1.ipynb, Example3.ipynb) as chunks of a batched solve.  `layers` as in `_solve_chunk`, with
     per-point quantities carrying a leading dimension B = len(freq).  Returns the requested S-parameter [B, len(orders)].
 
     eig_route: "auto" (mixed-precision eigensolver; once a chunk of THIS call had to redo matrices in fp64, the remaining layers and chunks
-    of this call use the all-fp64 route -- BatchedRCWA._eig_call), "mixed" or "fp64"."""
+    of this call use the all-fp64 route -- BatchedRCWA._eig_call), "mixed" or "fp64".
+
+    fourier_rule: "laurent" (default) or "li" (Li's inverse rule in every patterned layer, BatchedRCWA)."""
     from .engine import default_engine
+    if fourier_rule not in ("laurent", "li"):
+        raise ValueError(f"fourier_rule must be 'laurent' or 'li', got {fourier_rule!r}")
     B = freq.shape[0]
     eng = engine if engine is not None else default_engine()
     old_check, eng.check_info = eng.check_info, check_info         # restored below: the engine may be shared with other solvers
     # chunk=None: as many points in lock-step as the free HBM holds (the reference's per-point loop cannot run out of memory; neither must this)
-    chunk = auto_chunk(B, order, len(layers), precision, freq.device, dtype=dtype, streams=streams) if not chunk else int(chunk)
+    chunk = (auto_chunk(B, order, len(layers), precision, freq.device, dtype=dtype, streams=streams, fourier_rule=fourier_rule) if not chunk
+             else int(chunk))
     if streams > 1 and chunk >= B:
         chunk = -(-B // streams)
     spans = [(lo, min(B, lo + chunk)) for lo in range(0, B, chunk)]
@@ -157,7 +165,7 @@ def solve_stack_sweep(freq, layers, order, L, *, eps_in=None, eps_out=None, inc_
         lays = [tuple(_slice(v, lo, hi, B) for v in lay) for lay in layers]
         outs[i] = _solve_chunk(freq[lo:hi], lays, order, L, _slice(eps_in, lo, hi, B), _slice(eps_out, lo, hi, B), _slice(inc_ang, lo, hi, B),
                                _slice(azi_ang, lo, hi, B), dtype, precision, engine, orders, polarization, direction, port, check_info,
-                               eig_route=eig_route, route_hint=route_hint)
+                               eig_route=eig_route, route_hint=route_hint, fourier_rule=fourier_rule)
 
     dev = freq.device
     try:
@@ -198,7 +206,8 @@ def _run_spans(run, spans, streams, dev):
 
 
 def solve_single_layer_sweep(freq, eps_grids, thickness, order, L, **kw):
-    """B sweep points of a 1-patterned-layer stack (configs 2 and 4 of BASELINE.json): freq [B], eps_grids [B,nx,ny].
+    """B sweep points of a 1-patterned-layer stack (configs 2 and 4 of BASELINE.json): freq [B], eps_grids [B,nx,ny].  Keywords as
+    solve_stack_sweep (fourier_rule="li": Li's inverse rule).
 
     chunk   : points solved in lock-step by one batched solver (bounds the HBM footprint; default None = as many as the free HBM holds with
               10 % headroom, `auto_chunk`).  At order [15,15] (n = 1922) a point costs about 0.6 GB allocated / 0.9 GB reserved, so about 256 points
