@@ -66,6 +66,29 @@ size_t trx_convmat_li_ws_bytes(int dtype, int batch, int nx, int ny, int ox, int
 int trx_convmat_li(int dtype, int grid_is_complex, const void* grid, int batch, int nx, int ny, int ox, int oy, void* Ex, void* Ey,
                    void* Ux, void* Uy, int* info, void* ws, size_t ws_bytes, void* stream);
 
+/* ---- Fourier factorisation, normal-vector method (no reference counterpart) -----------------------------------------------------------
+ * Schuster et al., JOSA A 24, 2880 (2007); Goetz et al., Opt. Express 16, 17295 (2008).  For each grid[b] ([nx, ny], layout and index map as
+ * trx_convmat) and an in-plane unit field N normal to the material interfaces:
+ *   D = [eps] - [1/eps]^-1,   Exx = [eps] - {D, [Nx Nx]},   Exy (= Eyx) = -{D, [Nx Ny]},   Eyy = [eps] - {D, [Ny Ny]}
+ * ([f]: the Laurent convolution matrix of trx_convmat; {D, C} = (D C + C D)/2, the symmetrised product, which keeps the tensor Hermitian
+ * for a lossless grid -- with the plain product D C a lossless layer does not conserve energy at finite order).  Exx, Exy, Eyy: [batch,N,N] outputs in `dtype`; E_z keeps Laurent's [eps].
+ *
+ * trx_normal_field: the products nn[b] = (Nx^2, Nx Ny, Ny^2) ([batch,3,nx,ny] fp64) of the field derived from the grid.  J = Re(grad g grad g^H)
+ * from periodic central differences with grid spacings hx, hy (only their ratio matters: pass Lx/nx, Ly/ny), blurred along y and then x by
+ * the periodic Gaussian w[k] = exp(-k^2/(2 sigma^2)) / sum_k, |k| <= ceil(3 sigma) cells (sigma = 0: no blur); N = principal eigenvector of
+ * the blurred J:  with d = Jxx - Jyy, o = 2 Jxy, r = hypot(d, o):  Nx^2 = (1 + d/r)/2, Nx Ny = o/(2r), Ny^2 = (1 - d/r)/2 where
+ * r > 1e-3 (Jxx + Jyy) (a unit field); elsewhere 0, i.e. Laurent's rule.  grid in the real / complex type of `dtype`; 0 <= sigma <= 256,
+ * nx, ny <= 2048, else TRX_ERR_UNSUPPORTED.
+ * trx_convmat_nv: the tensor.  nn: optional [batch,3,nx,ny] fp64 product grids supplied by the caller (an analytic field); NULL = derive them
+ * from the grid (sigma, hx, hy as trx_normal_field; ignored otherwise).  info[batch] (device): 0 ok, 1 a grid value is zero, 2 [1/eps] is
+ * singular.  All arithmetic is fp64 for both dtypes ([1/eps]^-1 by trx_inverse in complex128).  Requires nx > 2ox, ny > 2oy, max(nx, ny) <= 2048. */
+size_t trx_normal_field_ws_bytes(int dtype, int batch, int nx, int ny);
+int trx_normal_field(int dtype, int grid_is_complex, const void* grid, int batch, int nx, int ny, double sigma, double hx, double hy, double* nn,
+                     void* ws, size_t ws_bytes, void* stream);
+size_t trx_convmat_nv_ws_bytes(int dtype, int batch, int nx, int ny, int ox, int oy);
+int trx_convmat_nv(int dtype, int grid_is_complex, const void* grid, int batch, int nx, int ny, int ox, int oy, double sigma, double hx, double hy,
+                   const double* nn, void* Exx, void* Exy, void* Eyy, int* info, void* ws, size_t ws_bytes, void* stream);
+
 /* ---- dense complex building blocks (the torch.matmul / torch.linalg.inv call sites, rcwa.py:1157-1304) -------- */
 /* C = alpha*op(A)*op(B) + beta*C, batched with element strides; alpha/beta point to HOST complex scalars. */
 int trx_gemm(int dtype, int opA, int opB, int m, int n, int k, const void* alpha, const void* A, int lda,
@@ -216,7 +239,7 @@ size_t trx_build_a_ws_bytes(int dtype, int N, int batch);
 int trx_build_a(int dtype, const void* E, const void* Einv, const void* mu, const void* kx, const void* ky, int N, int batch, void* A,
                 void* ws, size_t ws_bytes, void* stream);
 
-/* P, Q (as trx_build_pq) with a convolution matrix per field component (Li's rule; later also diagonal-anisotropic inputs):
+/* P, Q (as trx_build_pq) with a convolution matrix per field component (Li's rule; the full in-plane tensor: trx_build_pq_tensor):
  *   P = [[Kx Ei Ky, My - Kx Ei Kx],[Ky Ei Ky - Mx, -Ky Ei Kx]],  Q = [[-Kx Mi Ky, Kx Mi Kx - Ey],[Ex - Ky Mi Ky, Ky Mi Kx]]
  * Einv / Minv: inverses of the LAURENT matrices (they act on Ez / Hz).  Ex = Ey = E, Mx = My = M gives trx_build_pq. */
 int trx_build_pq_aniso(int dtype, const void* Ex, const void* Ey, const void* Einv, const void* Mx, const void* My, const void* Minv,
@@ -226,6 +249,18 @@ int trx_build_pq_aniso(int dtype, const void* Ex, const void* Ey, const void* Ei
 size_t trx_build_a_aniso_ws_bytes(int dtype, int N, int batch);
 int trx_build_a_aniso(int dtype, const void* Ex, const void* Ey, const void* Einv, const void* mu, const void* kx, const void* ky, int N, int batch,
                       void* A, void* ws, size_t ws_bytes, void* stream);
+
+/* P, Q (as trx_build_pq) with the in-plane permittivity tensor of trx_convmat_nv (Eyx = Exy):
+ *   P = [[Kx Ei Ky, M - Kx Ei Kx],[Ky Ei Ky - M, -Ky Ei Kx]],  Q = [[-Kx Mi Ky - Exy, Kx Mi Kx - Eyy],[Exx - Ky Mi Ky, Ky Mi Kx + Exy]]
+ * Einv: inverse of the LAURENT [eps] (it acts on Ez); Mu / Muinv as trx_build_pq.  Exx = Eyy = E, Exy = 0 gives trx_build_pq. */
+int trx_build_pq_tensor(int dtype, const void* Exx, const void* Exy, const void* Eyy, const void* Einv, const void* Mu, const void* Muinv,
+                        const void* kx, const void* ky, int N, int batch, void* P, void* Q, void* stream);
+/* A = P Q for homogeneous mu[batch] with the tensor (one N x 2N GEMM, the cost of trx_build_a_aniso's two N^3 products):
+ *   A = [[mu Exx - Ky^2 - Kx Gx, mu Exy + KxKy - Kx Gy],[mu Exy + KxKy - Ky Gx, mu Eyy - Kx^2 - Ky Gy]],
+ *   [Gx, Gy] = Einv [Kx Exx + Ky Exy, Kx Exy + Ky Eyy]. */
+size_t trx_build_a_tensor_ws_bytes(int dtype, int N, int batch);
+int trx_build_a_tensor(int dtype, const void* Exx, const void* Exy, const void* Eyy, const void* Einv, const void* mu, const void* kx, const void* ky,
+                       int N, int batch, void* A, void* ws, size_t ws_bytes, void* stream);
 
 /* ---- measurement aid (no reference counterpart): HIP-event timing of the dominant kernels --------------------
  * trx_prof_enable(1) makes the instrumented launch sites record hipEvents on the launch stream.  Sampling is systematic and

@@ -27,6 +27,16 @@ _SIGS = {
     "trx_build_a_aniso_ws_bytes": (c_size_t, [c_int, c_int, c_int]),
     "trx_build_a_aniso": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_size_t,
                                   c_void_p]),
+    "trx_normal_field_ws_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
+    "trx_normal_field": (c_int, [c_int, c_int, c_void_p, c_int, c_int, c_int, c_double, c_double, c_double, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "trx_convmat_nv_ws_bytes": (c_size_t, [c_int, c_int, c_int, c_int, c_int, c_int]),
+    "trx_convmat_nv": (c_int, [c_int, c_int, c_void_p, c_int, c_int, c_int, c_int, c_int, c_double, c_double, c_double, c_void_p, c_void_p, c_void_p,
+                               c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "trx_build_pq_tensor": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p,
+                                    c_void_p, c_void_p]),
+    "trx_build_a_tensor_ws_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "trx_build_a_tensor": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p,
+                                   c_size_t, c_void_p]),
     "trx_gemm": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_long, c_void_p, c_int, c_long,
                          c_void_p, c_void_p, c_int, c_long, c_int, c_void_p]),
     "trx_lu_solve": (c_int, [c_int, c_void_p, c_int, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p]),

@@ -23,6 +23,15 @@ _PORTS = {"t": "transmission", "transmission": "transmission", "r": "reflection"
 _SBLOCK = {("forward", "transmission"): 0, ("forward", "reflection"): 1, ("backward", "reflection"): 2, ("backward", "transmission"): 3}
 # (numerator side, denominator side) of the power normalisation for S[k]            rcwa.py:377-388
 _KZ_SIDES = {0: ("out", "in"), 1: ("in", "in"), 2: ("out", "out"), 3: ("in", "out")}
+FOURIER_RULES = ("laurent", "li", "normal")
+# fourier_rule="normal": default width (grid cells) of the Gaussian that smooths the structure tensor of a grid into the normal-vector field
+# (include/trx.h: trx_normal_field); chosen by the CPU study in profiles/normal_vector.txt
+NV_SIGMA_DEFAULT = 6.0
+
+
+def check_fourier_rule(rule):
+    if rule not in FOURIER_RULES:
+        raise ValueError(f"fourier_rule must be one of {FOURIER_RULES}, got {rule!r}")
 
 
 class BlockDiag2:
@@ -71,12 +80,17 @@ def _halfspace_V(kx, ky, epsmu):
 class BatchedRCWA:
     def __init__(self, freq, order, L, *, batch=None, dtype=torch.complex64, device=None, stable_eig_grad=True,
                  avoid_Pinv_instability=False, max_Pinv_instability=0.005, precision="high", engine=None,
-                 keep_coupling=True, fold_layers=False, eig_route="auto", route_hint=None, fourier_rule="laurent"):
-        if fourier_rule not in ("laurent", "li"):
-            raise ValueError(f"fourier_rule must be 'laurent' or 'li', got {fourier_rule!r}")
+                 keep_coupling=True, fold_layers=False, eig_route="auto", route_hint=None, fourier_rule="laurent", nv_sigma=NV_SIGMA_DEFAULT):
+        check_fourier_rule(fourier_rule)
         # fourier_rule="li": Li's inverse rule for the x / y components of D in every patterned layer (Ex, Ey convolution matrices,
         # include/trx.h trx_convmat_li); Ez / Hz keep Laurent's matrices (E^-1 in P, trx_hmodes, eps_conv).  "laurent": the reference's rule.
+        # fourier_rule="normal": the normal-vector method (in-plane tensor Exx, Exy, Eyy of the permittivity, trx_convmat_nv) with the field
+        # derived from each grid, smoothed over nv_sigma cells, unless add_layer(normal_field=...) supplies one; a patterned mu keeps
+        # Laurent's matrix, and so do Ez / Hz.
         self.fourier_rule = fourier_rule
+        self.nv_sigma = float(nv_sigma)
+        if not (0.0 <= self.nv_sigma <= 256.0):
+            raise ValueError(f"nv_sigma must lie in [0, 256] grid cells, got {nv_sigma!r}")
         if dtype != torch.complex64 and dtype != torch.complex128:                      # rcwa.py:37-41
             warnings.warn("Invalid simulation data type. Set as torch.complex64.", UserWarning)
             dtype = torch.complex64
@@ -122,6 +136,8 @@ class BatchedRCWA:
         self.thickness = []
         self.eps_conv, self.mu_conv = [], []
         self.eps_conv_x, self.eps_conv_y = [], []      # fourier_rule="li" with keep_coupling: Ex, Ey per layer (None: homogeneous / folded)
+        # fourier_rule="normal" with keep_coupling: Exx, Exy (= Eyx), Eyy per layer (None: homogeneous eps / folded)
+        self.eps_conv_xx, self.eps_conv_xy, self.eps_conv_yy = [], [], []
         self.P, self.Q = [], []
         self.kz_norm, self.E_eigvec, self.H_eigvec = [], [], []
         self.Cplus, self.Cminus = [], []
@@ -187,9 +203,16 @@ class BatchedRCWA:
             self._Sout = [(T @ self._Vf).scale(2), T @ D, -(T @ D), (T @ self._Vo).scale(2)]
 
     # ---- a4-a8 -------------------------------------------------------------------------------------------
-    def add_layer(self, thickness, eps=1., mu=1.):                                      # rcwa.py:146-170
+    def add_layer(self, thickness, eps=1., mu=1., normal_field=None):                  # rcwa.py:146-170
+        """normal_field (fourier_rule="normal" only): (Nx, Ny), each [nx, ny] or [B, nx, ny] on the eps grid, a caller-supplied in-plane field
+        for the normal-vector method (e.g. the analytic radial field of a disk), used as given (not normalised) and treated as constant by
+        autograd.  None: the field is derived from the eps grid (trx_normal_field, nv_sigma)."""
         eng, N, B, cdt = self.engine, self.order_N, self.B, self._cdtype
         eps_h, mu_h = self._is_homogeneous(eps), self._is_homogeneous(mu)
+        if normal_field is not None and self.fourier_rule != "normal":
+            raise ValueError('add_layer(normal_field=...) needs fourier_rule="normal"')
+        if normal_field is not None and eps_h:
+            raise ValueError("add_layer(normal_field=...) needs a patterned eps grid")
         eye = torch.eye(N, dtype=cdt, device=self._device)
         # differentiable path (Examples 4-6): every O(n^3) primitive is an autograd.Function over the same HIP kernels
         diff = torch.is_grad_enabled() and any(torch.is_tensor(v) and v.requires_grad for v in
@@ -219,6 +242,20 @@ class BatchedRCWA:
                 return ag.ConvMatLiFn.apply(g.contiguous(), self.order[0], self.order[1], cdt, eng)
             return eng.convmat_li(g.contiguous(), self.order[0], self.order[1], cdt)[:2]
 
+        def conv_nv(v):
+            """(Exx, Exy, Eyy) of a patterned eps grid with the normal-vector rule."""
+            g = torch.as_tensor(v, device=self._device)
+            if g.dim() == 2:
+                g = g[None].expand(B, -1, -1)
+            g = g.contiguous()
+            nn = self._nv_products(g, normal_field)
+            hx, hy = self._nv_spacing(g)
+            if diff:
+                if nn is None:                 # the field derived from the grid is a constant of the differentiable path (detached)
+                    nn = eng.normal_field(g.detach(), self.nv_sigma, hx, hy)
+                return self._nv_tensor_torch(g, nn)
+            return eng.convmat_nv(g, self.order[0], self.order[1], cdt, sigma=self.nv_sigma, hx=hx, hy=hy, nn=nn)
+
         if eps_h and mu_h and not diff and not self.keep_coupling:
             self._add_homogeneous_layer_bd(thickness, self._bvec(eps), self._bvec(mu))
             self._fold_last_layer()
@@ -235,11 +272,19 @@ class BatchedRCWA:
         li = self.fourier_rule == "li" and not (eps_h and mu_h)
         Ex, Ey = conv_li(eps, eps_h, E) if li else (None, None)
         Mx, My = conv_li(mu, mu_h, M) if (li and M is not None) else (None, None)
+        nv = self.fourier_rule == "normal" and not eps_h          # a homogeneous eps has the tensor eps I: Laurent's matrices as they are
+        Exy = None
+        if nv:
+            Ex, Exy, Ey = conv_nv(eps)
         self.eps_conv.append(E)
         self.mu_conv.append(M)
         keep_li = li and self.keep_coupling and not eps_h
         self.eps_conv_x.append(Ex if keep_li else None)
         self.eps_conv_y.append(Ey if keep_li else None)
+        keep_nv = nv and self.keep_coupling
+        self.eps_conv_xx.append(Ex if keep_nv else None)
+        self.eps_conv_xy.append(Exy if keep_nv else None)
+        self.eps_conv_yy.append(Ey if keep_nv else None)
         self.layer_N += 1
         d = self._bvec(thickness, self._rdtype)
         self.thickness.append(d)
@@ -250,9 +295,11 @@ class BatchedRCWA:
         if Minv is None and M is not None:
             Minv = inv(M)
         if diff:
-            P, Q = self._pq_torch(E, Einv, M, Minv, kxd, kyd, Ex, Ey, Mx, My)
+            P, Q = self._pq_torch(E, Einv, M, Minv, kxd, kyd, Ex, Ey, Mx, My, Exy)
         elif lean:
             P = Q = None
+        elif nv:
+            P, Q = eng.build_pq_tensor(Ex, Exy, Ey, Einv, M, Minv, kxd, kyd)
         elif li:
             P, Q = eng.build_pq_aniso(Ex, Ey, Einv, Mx, My, Minv, kxd, kyd)
         else:
@@ -271,11 +318,14 @@ class BatchedRCWA:
                 lam, W = Eig.apply(A) if self.stable_eig_grad else Eig.apply(A, Eig.UNBROADENED)
             else:
                 # A = P Q (rcwa.py:1236): with homogeneous mu the block structure needs two N^3 products, not one (2N)^3
-                if li:
+                if nv:
+                    A = eng.build_a_tensor(Ex, Exy, Ey, Einv, mu_s, kxd, kyd) if mu_h else eng.gemm(P, Q)
+                elif li:
                     A = eng.build_a_aniso(Ex, Ey, Einv, mu_s, kxd, kyd) if mu_h else eng.gemm(P, Q)
                 else:
                     A = eng.build_a(E, Einv, mu_s, kxd, kyd) if mu_h else eng.gemm(P, Q)
-                del Einv, Ex, Ey, Mx, My          # Li's matrices live on only in eps_conv_x / eps_conv_y (keep_coupling)
+                # Li's / the normal-vector matrices live on only in eps_conv_x / _y / _xx / _xy / _yy (keep_coupling)
+                del Einv, Ex, Ey, Mx, My, Exy
                 # mixed-precision eigensolver: two Newton steps for a complex64 problem (1e-5 gate), three for complex128 (engine.eig)
                 lam, W = self._eig_call(A, refine_steps=3 if self._dtype == torch.complex128 else 2)      # torch_eig.py:14
                 del A
@@ -308,6 +358,7 @@ class BatchedRCWA:
         self.layer_S11[i] = self.layer_S21[i] = None
         self.eps_conv[i] = None
         self.eps_conv_x[i] = self.eps_conv_y[i] = None
+        self.eps_conv_xx[i] = self.eps_conv_xy[i] = self.eps_conv_yy[i] = None
         self._n_folded = i + 1
 
     def _add_homogeneous_layer_bd(self, thickness, eps_s, mu_s):
@@ -333,14 +384,41 @@ class BatchedRCWA:
         self.layer_N += 1
         self.thickness.append(d)
         self.kz_norm.append(torch.cat((kz, kz), dim=1))
-        for lst in (self.eps_conv, self.mu_conv, self.eps_conv_x, self.eps_conv_y, self.P, self.Q, self.E_eigvec, self.H_eigvec, self.Cplus,
-                    self.Cminus):
+        for lst in (self.eps_conv, self.mu_conv, self.eps_conv_x, self.eps_conv_y, self.eps_conv_xx, self.eps_conv_xy, self.eps_conv_yy,
+                    self.P, self.Q, self.E_eigvec, self.H_eigvec, self.Cplus, self.Cminus):
             lst.append(None)
 
+    def _nv_spacing(self, g):
+        """Grid spacings (hx, hy) of a [B, nx, ny] grid over the unit cell: they orient the gradient of the normal-vector field."""
+        return float(self.L[0]) / g.shape[1], float(self.L[1]) / g.shape[2]
+
+    def _nv_products(self, g, normal_field):
+        """[B,3,nx,ny] float64 (Nx^2, Nx Ny, Ny^2): from a caller-supplied field, or None (the library derives it from the grid)."""
+        if normal_field is None:
+            return None
+        Nx, Ny = (torch.as_tensor(t, device=self._device).detach().to(torch.float64) for t in normal_field)
+        shp = tuple(g.shape[1:])
+        if tuple(Nx.shape[-2:]) != shp or tuple(Ny.shape[-2:]) != shp:
+            raise ValueError(f"normal_field components must be {list(shp)} grids like eps, got {list(Nx.shape)} and {list(Ny.shape)}")
+        Nx, Ny = Nx.expand(self.B, -1, -1), Ny.expand(self.B, -1, -1)
+        return torch.stack((Nx * Nx, Nx * Ny, Ny * Ny), dim=1).contiguous()
+
+    def _nv_tensor_torch(self, g, nn):
+        """(Exx, Exy, Eyy) from the differentiable primitives: ConvMatFn of eps and 1/eps, InverseFn, GemmFn (the symmetrised products
+        (D C + C D) / 2 of include/trx.h: trx_convmat_nv); the field products nn are constants."""
+        eng, cdt, (ox, oy) = self.engine, self._cdtype, self.order
+        B = g.shape[0]
+        E = ag.ConvMatFn.apply(g, ox, oy, cdt, eng)
+        D = E - ag.InverseFn.apply(ag.ConvMatFn.apply((1 / g).contiguous(), ox, oy, cdt, eng), eng)
+        C = eng.convmat(nn.reshape(3 * B, *nn.shape[2:]), ox, oy, cdt).reshape(B, 3, E.shape[1], E.shape[2])
+        DC = [0.5 * (ag.GemmFn.apply(D, C[:, c].contiguous(), eng) + ag.GemmFn.apply(C[:, c].contiguous(), D, eng)) for c in range(3)]
+        return E - DC[0], -DC[1], E - DC[2]
+
     @staticmethod
-    def _pq_torch(E, Ei, M, Mi, kx, ky, Ex=None, Ey=None, Mx=None, My=None):
+    def _pq_torch(E, Ei, M, Mi, kx, ky, Ex=None, Ey=None, Mx=None, My=None, Exy=None):
         """P, Q (rcwa.py:1226-1232) with broadcasting instead of dense diagonal products (differentiable).  Ex, Ey, Mx, My: Li's
-        per-component matrices (default: the Laurent E, M in both places)."""
+        per-component matrices (default: the Laurent E, M in both places); with Exy, (Ex, Exy, Ey) is the normal-vector tensor
+        (Exx, Exy = Eyx, Eyy) and Q gains its off-diagonal blocks."""
         Ex, Ey = (E, E) if Ex is None else (Ex, Ey)
         Mx, My = (M, M) if Mx is None else (Mx, My)
         kxi, kyi, kxj, kyj = kx[:, :, None], ky[:, :, None], kx[:, None, :], ky[:, None, :]
@@ -348,6 +426,8 @@ class BatchedRCWA:
                        torch.cat((kyi * Ei * kyj - Mx, -(kyi * Ei * kxj)), dim=2)), dim=1)
         Q = torch.cat((torch.cat((-(kxi * Mi * kyj), kxi * Mi * kxj - Ey), dim=2),
                        torch.cat((Ex - kyi * Mi * kyj, kyi * Mi * kxj), dim=2)), dim=1)
+        if Exy is not None:
+            Q = Q + torch.cat((torch.cat((-Exy, torch.zeros_like(Exy)), dim=2), torch.cat((torch.zeros_like(Exy), Exy), dim=2)), dim=1)
         return P, Q
 
     def _solve_layer_smatrix_diff(self):

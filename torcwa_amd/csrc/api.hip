@@ -3,7 +3,7 @@
 
 using namespace trx;
 
-extern "C" int trx_version(void) { return 200; }   // 0.2.0: trx_convmat_li, trx_build_pq_aniso, trx_build_a_aniso
+extern "C" int trx_version(void) { return 300; }   // 0.3.0: trx_normal_field, trx_convmat_nv, trx_build_pq_tensor, trx_build_a_tensor
 
 extern "C" const char* trx_strerror(int code) {
     switch (code) {

@@ -1,0 +1,432 @@
+// Fourier factorisation, normal-vector method (Schuster et al., JOSA A 24, 2880 (2007); Goetz et al., Opt. Express 16, 17295 (2008)):
+// permittivity grid -> the in-plane 2 x 2 tensor of convolution matrices of a patterned layer with curved or oblique boundaries.
+//
+//   N(x, y): smooth in-plane unit field normal to the material interfaces (only N N^T enters, so the sign of N does not matter);
+//   D = [eps] - [1/eps]^-1;   Exx = [eps] - {D, [Nx Nx]},   Exy = Eyx = -{D, [Nx Ny]},   Eyy = [eps] - {D, [Ny Ny]}
+//   ([f]: Laurent's Toeplitz convolution matrix of a grid, trx_convmat; {D, C} = (D C + C D) / 2, the symmetrised product: D and C are
+//   Hermitian for a lossless grid, and so is then the tensor -- the plain product D C is not, and breaks energy conservation at finite order).
+//
+// The field (trx_normal_field) comes from the grid itself:
+//   1. structure tensor J = Re(grad eps grad eps^H) from periodic central differences (grid spacings hx, hy): independent of the
+//      complex contrast, so metals work;
+//   2. J blurred by a separable, truncated (radius ceil(3 sigma)), periodic Gaussian of width sigma cells: a pass along y with the
+//      row in LDS, then a pass along x with lanes over y (coalesced rows);
+//   3. N = principal eigenvector of the blurred J, in closed form: with d = Jxx - Jyy, o = 2 Jxy, r = hypot(d, o),
+//      Nx^2 = (1 + d/r)/2, Nx Ny = o/(2r), Ny^2 = (1 - d/r)/2 -- a unit field wherever the coherence r / (Jxx + Jyy) exceeds
+//      NV_TAU; elsewhere (uniform regions farther than the blur radius from any edge, isotropic points) N N^T = 0, i.e. Laurent's rule
+//      (the fallback chosen by the study in profiles/normal_vector.txt).
+// trx_convmat_nv chains the field, trx_convmat of eps, of 1/eps and of the three product grids, the inverse of [1/eps] (trx_inverse,
+// complex128) and the six GEMMs of the three symmetrised products; all of it in fp64 for both dtypes.
+// Also here: P, Q and A = PQ of a layer whose in-plane permittivity is the full tensor.
+#include <algorithm>
+#include <cmath>
+
+#include "common.hpp"
+
+namespace trx {
+namespace {
+
+typedef cx<double> zc;
+
+constexpr double NV_TAU = 1e-3;          // coherence floor of a resolvable direction
+constexpr double NV_SIGMA_MAX = 256.0;   // blur radius ceil(3 sigma) <= 768 cells: the weights stay a small LDS table
+
+static inline int nv_radius(double sigma) { return sigma > 0.0 ? (int)std::ceil(3.0 * sigma) : 0; }
+
+// w[k + R] = exp(-k^2 / (2 sigma^2)) / sum, k in [-R, R]  (every workgroup builds its own copy in LDS)
+__device__ void nv_weights(double sigma, int R, double* w) {
+    for (int k = threadIdx.x; k <= 2 * R; k += blockDim.x) {
+        const double t = (double)(k - R);
+        w[k] = R > 0 ? exp(-t * t / (2.0 * sigma * sigma)) : 1.0;
+    }
+    __syncthreads();
+    double s = 0.0;                                // every thread sums in the same order: one normaliser for the workgroup
+    for (int k = 0; k <= 2 * R; ++k) s += w[k];
+    __syncthreads();
+    for (int k = threadIdx.x; k <= 2 * R; k += blockDim.x) w[k] /= s;
+    __syncthreads();
+}
+
+static inline __device__ int wrap(int i, int n) {
+    i %= n;
+    return i < 0 ? i + n : i;
+}
+
+// g (T, real or complex) -> gz = g, rz = 1/g in complex128; a zero value sets info[b] = 1 (rz may be NULL)
+template <class T, bool CPLX>
+__global__ __launch_bounds__(256) void nv_convert_kernel(const T* __restrict__ grid, long per, zc* __restrict__ gz, zc* __restrict__ rz,
+                                                         int* __restrict__ info) {
+    const int b = blockIdx.y;
+    const long e = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= per) return;
+    const long o = (long)b * per + e;
+    const zc v = CPLX ? zc((double)grid[2 * o], (double)grid[2 * o + 1]) : zc((double)grid[o], 0.0);
+    gz[o] = v;
+    if (rz) {
+        if (v.x == 0.0 && v.y == 0.0) info[b] = 1;
+        rz[o] = crecip(v);
+    }
+}
+
+// Structure tensor of grid row x, blurred along y:  Jy[b, c, x, y] = sum_k w[k] J_c[x, y+k]   (c = xx, xy, yy)
+__global__ __launch_bounds__(256) void nv_tensor_y_kernel(const zc* __restrict__ g, int nx, int ny, double sigma, int R, double rhx, double rhy,
+                                                          double* __restrict__ Jy) {
+    TRX_DYN_SMEM(smem);
+    double* J = reinterpret_cast<double*>(smem);   // [3][ny]
+    double* w = J + 3 * ny;                        // [2R+1]
+    const int x = blockIdx.x, b = blockIdx.y;
+    const zc* gb = g + (long)b * nx * ny;
+    const zc* r0 = gb + (long)x * ny;
+    const zc* rm = gb + (long)wrap(x - 1, nx) * ny;
+    const zc* rp = gb + (long)wrap(x + 1, nx) * ny;
+    for (int y = threadIdx.x; y < ny; y += blockDim.x) {
+        const zc gx = (0.5 * rhx) * (rp[y] - rm[y]);
+        const zc gy = (0.5 * rhy) * (r0[wrap(y + 1, ny)] - r0[wrap(y - 1, ny)]);
+        J[y] = norm2(gx);
+        J[ny + y] = gx.x * gy.x + gx.y * gy.y;     // Re(gx conj(gy))
+        J[2 * ny + y] = norm2(gy);
+    }
+    nv_weights(sigma, R, w);                       // (ends with a barrier: J is visible too)
+    const long nxy = (long)nx * ny;
+    for (int y = threadIdx.x; y < ny; y += blockDim.x) {
+        double a0 = 0.0, a1 = 0.0, a2 = 0.0;
+        for (int k = -R; k <= R; ++k) {
+            const int yy = wrap(y + k, ny);
+            const double wk = w[k + R];
+            a0 = fma(wk, J[yy], a0);
+            a1 = fma(wk, J[ny + yy], a1);
+            a2 = fma(wk, J[2 * ny + yy], a2);
+        }
+        double* o = Jy + (long)b * 3 * nxy + (long)x * ny + y;
+        o[0] = a0;
+        o[nxy] = a1;
+        o[2 * nxy] = a2;
+    }
+}
+
+// Blur along x and the closed-form principal direction:  nn[b, c, x, y] = (Nx^2, Nx Ny, Ny^2).  256 threads = 4 waves; lane = y
+// (64 consecutive grid columns: every load of the k loop is a coalesced row segment), wave = one of 4 consecutive x.
+__global__ __launch_bounds__(256) void nv_field_x_kernel(const double* __restrict__ Jy, int nx, int ny, double sigma, int R,
+                                                         double* __restrict__ nn) {
+    TRX_DYN_SMEM(smem);
+    double* w = reinterpret_cast<double*>(smem);   // [2R+1]
+    nv_weights(sigma, R, w);
+    const int b = blockIdx.z;
+    const int y = blockIdx.x * 64 + (threadIdx.x & 63);
+    const int x = blockIdx.y * 4 + (threadIdx.x >> 6);
+    if (y >= ny || x >= nx) return;
+    const long nxy = (long)nx * ny;
+    const double* J = Jy + (long)b * 3 * nxy;
+    double a0 = 0.0, a1 = 0.0, a2 = 0.0;
+    for (int k = -R; k <= R; ++k) {
+        const long e = (long)wrap(x + k, nx) * ny + y;
+        const double wk = w[k + R];
+        a0 = fma(wk, J[e], a0);
+        a1 = fma(wk, J[nxy + e], a1);
+        a2 = fma(wk, J[2 * nxy + e], a2);
+    }
+    const double d = a0 - a2, o = 2.0 * a1;
+    const double r = sqrt(d * d + o * o);
+    double pxx = 0.0, pxy = 0.0, pyy = 0.0;       // fallback: N N^T = 0 (Laurent's rule where no direction is resolvable)
+    if (r > NV_TAU * (a0 + a2)) {
+        const double c = d / r;
+        pxx = 0.5 * (1.0 + c);
+        pxy = 0.5 * (o / r);
+        pyy = 0.5 * (1.0 - c);
+    }
+    double* out = nn + (long)b * 3 * nxy + (long)x * ny + y;
+    out[0] = pxx;
+    out[nxy] = pxy;
+    out[2 * nxy] = pyy;
+}
+
+__global__ __launch_bounds__(256) void nv_delta_kernel(const zc* __restrict__ E, zc* __restrict__ D, long n) {
+    const long e = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (e < n) D[e] = E[e] - D[e];                 // D <- [eps] - [1/eps]^-1
+}
+
+__global__ __launch_bounds__(256) void nv_info_kernel(const int* __restrict__ inv_info, int batch, int* __restrict__ info) {
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b < batch && info[b] == 0 && inv_info[b] != 0) info[b] = 2;
+}
+
+template <class T>
+__global__ __launch_bounds__(256) void nv_store_kernel(const zc* __restrict__ in, cx<T>* __restrict__ out, long n) {
+    const long e = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (e < n) out[e] = cx<T>((T)in[e].x, (T)in[e].y);
+}
+
+static inline size_t al256(size_t b) { return (b + 255) & ~(size_t)255; }
+
+// workspace of the field from a complex128 grid: the y-blurred tensor [B, 3, nx, ny] fp64
+static inline size_t field_core_bytes(int batch, int nx, int ny) { return al256(sizeof(double) * 3 * (size_t)batch * nx * ny); }
+
+int field_core(hipStream_t s, const zc* gz, int batch, int nx, int ny, double sigma, double hx, double hy, double* nn, double* Jy) {
+    const int R = nv_radius(sigma);
+    const size_t lds1 = sizeof(double) * (3 * (size_t)ny + 2 * R + 1), lds2 = sizeof(double) * (2 * (size_t)R + 1);
+    if (set_max_dyn_smem((const void*)nv_tensor_y_kernel, lds1)) return TRX_ERR_LAUNCH;
+    TRX_LAUNCH(nv_tensor_y_kernel, dim3(nx, batch), dim3(256), lds1, s, gz, nx, ny, sigma, R, 1.0 / hx, 1.0 / hy, Jy);
+    TRX_LAUNCH(nv_field_x_kernel, dim3(cdiv_i(ny, 64), cdiv_i(nx, 4), batch), dim3(256), lds2, s, (const double*)Jy, nx, ny, sigma, R, nn);
+    TRX_CHECK_LAUNCH();
+    return TRX_OK;
+}
+
+template <class T>
+int convert(hipStream_t s, int cplx, const void* grid, int batch, long per, zc* gz, zc* rz, int* info) {
+    const dim3 g(cdiv_i(per, 256), batch);
+    if (cplx) TRX_LAUNCH((nv_convert_kernel<T, true>), g, dim3(256), 0, s, (const T*)grid, per, gz, rz, info);
+    else      TRX_LAUNCH((nv_convert_kernel<T, false>), g, dim3(256), 0, s, (const T*)grid, per, gz, rz, info);
+    TRX_CHECK_LAUNCH();
+    return TRX_OK;
+}
+
+bool field_args_ok(int batch, int nx, int ny, double sigma, double hx, double hy) {
+    return batch > 0 && nx > 0 && ny > 0 && std::isfinite(sigma) && sigma >= 0.0 && std::isfinite(hx) && std::isfinite(hy) && hx > 0.0 &&
+           hy > 0.0;
+}
+
+struct NvLayout {                   // byte offsets into the workspace of trx_convmat_nv
+    size_t gz, rz, nn, jy, cws, R, C, inv, piv, iinfo, tmp, total;
+    size_t cws_bytes, inv_bytes;
+};
+
+NvLayout nv_layout(int dtype, int batch, int nx, int ny, int ox, int oy) {
+    NvLayout L;
+    const size_t per = (size_t)nx * ny, N = (size_t)(2 * ox + 1) * (2 * oy + 1), NN = N * N, B = (size_t)batch;
+    size_t o = 0;
+    L.gz = o;  o += al256(sizeof(zc) * B * per);
+    L.rz = o;  o += al256(sizeof(zc) * B * per);
+    L.nn = o;  o += al256(sizeof(double) * 3 * B * per);            // the field, when the caller supplies none
+    L.jy = o;  o += field_core_bytes(batch, nx, ny);
+    L.cws_bytes = trx_convmat_ws_bytes(TRX_C128, 3 * batch, nx, ny, ox, oy);
+    L.cws = o; o += al256(L.cws_bytes);
+    L.R = o;   o += al256(sizeof(zc) * B * NN);                     // [1/eps], then its inverse, then D
+    L.C = o;   o += al256(sizeof(zc) * 3 * B * NN);                 // [Nx^2], [Nx Ny], [Ny^2]
+    L.inv_bytes = trx_inverse_ws_bytes(TRX_C128, (int)N, batch);
+    L.inv = o; o += al256(L.inv_bytes);
+    L.piv = o; o += al256(sizeof(int) * B * N);
+    L.iinfo = o; o += al256(sizeof(int) * B);
+    L.tmp = o; o += dtype == TRX_C64 ? al256(sizeof(zc) * 3 * B * NN) : 0;   // complex128 results of a complex64 call
+    L.total = o;
+    return L;
+}
+
+template <class T>
+int convmat_nv_t(int cplx, const void* grid, int batch, int nx, int ny, int ox, int oy, double sigma, double hx, double hy, const double* nn_in,
+                 void* Exx, void* Exy, void* Eyy, int* info, char* ws, int dtype, hipStream_t s) {
+    const NvLayout L = nv_layout(dtype, batch, nx, ny, ox, oy);
+    const long per = (long)nx * ny;
+    const int N = (2 * ox + 1) * (2 * oy + 1);
+    const long NN = (long)N * N, bNN = (long)batch * NN;
+    zc* gz = (zc*)(ws + L.gz);
+    zc* rz = (zc*)(ws + L.rz);
+    zc* R = (zc*)(ws + L.R);
+    zc* C = (zc*)(ws + L.C);
+    int* piv = (int*)(ws + L.piv);
+    int* iinfo = (int*)(ws + L.iinfo);
+    zc *oxx, *oxy, *oyy;
+    if (dtype == TRX_C128) {
+        oxx = (zc*)Exx; oxy = (zc*)Exy; oyy = (zc*)Eyy;
+    } else {
+        oxx = (zc*)(ws + L.tmp); oxy = oxx + bNN; oyy = oxy + bNN;
+    }
+    if (hipMemsetAsync(info, 0, sizeof(int) * (size_t)batch, s) != hipSuccess) return TRX_ERR_LAUNCH;
+    int rc = convert<T>(s, cplx, grid, batch, per, gz, rz, info);
+    if (rc) return rc;
+    const double* nn = nn_in;
+    if (!nn) {
+        double* nw = (double*)(ws + L.nn);
+        rc = field_core(s, gz, batch, nx, ny, sigma, hx, hy, nw, (double*)(ws + L.jy));
+        if (rc) return rc;
+        nn = nw;
+    }
+    void* cws = ws + L.cws;
+    // [eps] -> Exx (copied to Eyy below), [1/eps] -> R, [N_c] -> C[b*3 + c]
+    if ((rc = trx_convmat(TRX_C128, 1, gz, batch, nx, ny, ox, oy, oxx, cws, L.cws_bytes, s))) return rc;
+    if ((rc = trx_convmat(TRX_C128, 1, rz, batch, nx, ny, ox, oy, R, cws, L.cws_bytes, s))) return rc;
+    if ((rc = trx_convmat(TRX_C128, 0, nn, 3 * batch, nx, ny, ox, oy, C, cws, L.cws_bytes, s))) return rc;
+    if (hipMemcpyAsync(oyy, oxx, sizeof(zc) * (size_t)bNN, hipMemcpyDeviceToDevice, s) != hipSuccess) return TRX_ERR_LAUNCH;
+    if ((rc = trx_inverse(TRX_C128, R, N, batch, piv, iinfo, ws + L.inv, L.inv_bytes, s))) return rc;
+    TRX_LAUNCH(nv_info_kernel, dim3(cdiv_i(batch, 256)), dim3(256), 0, s, (const int*)iinfo, batch, info);
+    TRX_LAUNCH(nv_delta_kernel, dim3(cdiv_i(bNN, 256)), dim3(256), 0, s, (const zc*)oxx, R, bNN);
+    TRX_CHECK_LAUNCH();
+    // Exx = [eps] - (D [Nx^2] + [Nx^2] D) / 2,  Exy = -(D [Nx Ny] + [Nx Ny] D) / 2,  Eyy = [eps] - (D [Ny^2] + [Ny^2] D) / 2
+    const zc mh(-0.5, 0.0), one(1.0, 0.0), zero(0.0, 0.0);
+    zc* out[3] = {oxx, oxy, oyy};
+    for (int c = 0; c < 3; ++c) {
+        if ((rc = gemm<double>(s, TRX_OP_N, TRX_OP_N, N, N, N, mh, R, N, NN, C + c * NN, N, 3 * NN, c == 1 ? zero : one, out[c], N, NN, batch)))
+            return rc;
+        if ((rc = gemm<double>(s, TRX_OP_N, TRX_OP_N, N, N, N, mh, C + c * NN, N, 3 * NN, R, N, NN, one, out[c], N, NN, batch))) return rc;
+    }
+    if (dtype == TRX_C64) {
+        const dim3 g(cdiv_i(bNN, 256));
+        TRX_LAUNCH((nv_store_kernel<float>), g, dim3(256), 0, s, (const zc*)oxx, (cx<float>*)Exx, bNN);
+        TRX_LAUNCH((nv_store_kernel<float>), g, dim3(256), 0, s, (const zc*)oxy, (cx<float>*)Exy, bNN);
+        TRX_LAUNCH((nv_store_kernel<float>), g, dim3(256), 0, s, (const zc*)oyy, (cx<float>*)Eyy, bNN);
+        TRX_CHECK_LAUNCH();
+    }
+    return TRX_OK;
+}
+
+// ---- P, Q and A = PQ with the in-plane permittivity tensor ---------------------------------------------------------------------------
+// P = [[Kx Ei Ky, M - Kx Ei Kx], [Ky Ei Ky - M, -Ky Ei Kx]],  Q = [[-Kx Mi Ky - Exy, Kx Mi Kx - Eyy], [Exx - Ky Mi Ky, Ky Mi Kx + Exy]]
+template <class T>
+__global__ __launch_bounds__(256) void build_pq_tensor_kernel(const cx<T>* __restrict__ Exx, const cx<T>* __restrict__ Exy,
+                                                              const cx<T>* __restrict__ Eyy, const cx<T>* __restrict__ Ei,
+                                                              const cx<T>* __restrict__ M, const cx<T>* __restrict__ Mi,
+                                                              const cx<T>* __restrict__ kx, const cx<T>* __restrict__ ky, int N,
+                                                              cx<T>* __restrict__ P, cx<T>* __restrict__ Q) {
+    const int b = blockIdx.z, i = blockIdx.y;
+    const int j = blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= N) return;
+    const long o = ((long)b * N + i) * N + j;
+    const cx<T> exx = Exx[o], exy = Exy[o], eyy = Eyy[o], ei = Ei[o], m = M[o], mi = Mi[o];
+    const cx<T> kxi = kx[(long)b * N + i], kyi = ky[(long)b * N + i], kxj = kx[(long)b * N + j], kyj = ky[(long)b * N + j];
+    const int n = 2 * N;
+    cx<T>* Pb = P + (long)b * n * n;
+    cx<T>* Qb = Q + (long)b * n * n;
+    const long r0 = (long)i * n + j, r1 = (long)(i + N) * n + j;
+    Pb[r0] = kxi * ei * kyj;
+    Pb[r0 + N] = m - kxi * ei * kxj;
+    Pb[r1] = kyi * ei * kyj - m;
+    Pb[r1 + N] = -(kyi * ei * kxj);
+    Qb[r0] = -(kxi * mi * kyj) - exy;
+    Qb[r0 + N] = kxi * mi * kxj - eyy;
+    Qb[r1] = exx - kyi * mi * kyj;
+    Qb[r1 + N] = kyi * mi * kxj + exy;
+}
+
+// A = PQ for homogeneous mu:
+//   [[mu Exx - Ky^2 - Kx Gx, mu Exy + Kx Ky - Kx Gy], [mu Exy + Kx Ky - Ky Gx, mu Eyy - Kx^2 - Ky Gy]],
+//   [Gx, Gy] = Ei S,  S = [Kx Exx + Ky Exy, Kx Exy + Ky Eyy]   (one N x 2N product)
+template <class T>
+__global__ __launch_bounds__(256) void nv_s_kernel(const cx<T>* __restrict__ Exx, const cx<T>* __restrict__ Exy, const cx<T>* __restrict__ Eyy,
+                                                   const cx<T>* __restrict__ kx, const cx<T>* __restrict__ ky, int N, cx<T>* __restrict__ S) {
+    const int b = blockIdx.z, i = blockIdx.y;
+    const int j = blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= N) return;
+    const long o = ((long)b * N + i) * N + j;
+    const cx<T> kxi = kx[(long)b * N + i], kyi = ky[(long)b * N + i], exy = Exy[o];
+    cx<T>* Sr = S + ((long)b * N + i) * 2 * N;
+    Sr[j] = kxi * Exx[o] + kyi * exy;
+    Sr[j + N] = kxi * exy + kyi * Eyy[o];
+}
+template <class T>
+__global__ __launch_bounds__(256) void assemble_a_tensor_kernel(const cx<T>* __restrict__ Exx, const cx<T>* __restrict__ Exy,
+                                                                const cx<T>* __restrict__ Eyy, const cx<T>* __restrict__ G,
+                                                                const cx<T>* __restrict__ mu, const cx<T>* __restrict__ kx,
+                                                                const cx<T>* __restrict__ ky, int N, cx<T>* __restrict__ A) {
+    const int b = blockIdx.z, i = blockIdx.y;
+    const int j = blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= N) return;
+    const long o = ((long)b * N + i) * N + j;
+    const cx<T> kxi = kx[(long)b * N + i], kyi = ky[(long)b * N + i], m = mu[b];
+    const cx<T>* Gr = G + ((long)b * N + i) * 2 * N;
+    const cx<T> gx = Gr[j], gy = Gr[j + N], mxy = m * Exy[o];
+    const int n = 2 * N;
+    cx<T>* Ab = A + (long)b * n * n;
+    cx<T> a11 = m * Exx[o] - kxi * gx, a12 = mxy - kxi * gy, a21 = mxy - kyi * gx, a22 = m * Eyy[o] - kyi * gy;
+    if (i == j) { a11 -= kyi * kyi; a22 -= kxi * kxi; a12 += kxi * kyi; a21 += kxi * kyi; }
+    Ab[(long)i * n + j] = a11;
+    Ab[(long)i * n + j + N] = a12;
+    Ab[(long)(i + N) * n + j] = a21;
+    Ab[(long)(i + N) * n + j + N] = a22;
+}
+template <class T>
+int build_a_tensor_t(hipStream_t s, const cx<T>* Exx, const cx<T>* Exy, const cx<T>* Eyy, const cx<T>* Ei, const cx<T>* mu, const cx<T>* kx,
+                     const cx<T>* ky, int N, int batch, cx<T>* A, cx<T>* ws) {
+    const long NN = (long)N * N, bNN2 = 2L * batch * NN;
+    const cx<T> one(T(1), T(0)), zero(T(0), T(0));
+    const dim3 g(cdiv_i(N, 256), N, batch), blk(256);
+    cx<T>*S = ws, *G = ws + bNN2;
+    TRX_LAUNCH((nv_s_kernel<T>), g, blk, 0, s, Exx, Exy, Eyy, kx, ky, N, S);
+    int rc = gemm<T>(s, TRX_OP_N, TRX_OP_N, N, 2 * N, N, one, Ei, N, NN, S, 2 * N, 2 * NN, zero, G, 2 * N, 2 * NN, batch);
+    if (rc) return rc;
+    TRX_LAUNCH((assemble_a_tensor_kernel<T>), g, blk, 0, s, Exx, Exy, Eyy, (const cx<T>*)G, mu, kx, ky, N, A);
+    TRX_CHECK_LAUNCH();
+    return TRX_OK;
+}
+
+}  // namespace
+}  // namespace trx
+
+using namespace trx;
+
+extern "C" size_t trx_normal_field_ws_bytes(int dtype, int batch, int nx, int ny) {
+    (void)dtype;
+    if (batch <= 0 || nx <= 0 || ny <= 0) return 0;
+    return al256(sizeof(zc) * (size_t)batch * nx * ny) + field_core_bytes(batch, nx, ny);
+}
+
+extern "C" int trx_normal_field(int dtype, int grid_is_complex, const void* grid, int batch, int nx, int ny, double sigma, double hx, double hy,
+                                double* nn, void* ws, size_t ws_bytes, void* stream) {
+    if (!grid || !nn || !ws || !field_args_ok(batch, nx, ny, sigma, hx, hy)) return TRX_ERR_ARG;
+    if (dtype != TRX_C64 && dtype != TRX_C128) return TRX_ERR_DTYPE;
+    if (ws_bytes < trx_normal_field_ws_bytes(dtype, batch, nx, ny)) return TRX_ERR_WORKSPACE;
+    if (nx > 2048 || ny > 2048 || sigma > NV_SIGMA_MAX) return TRX_ERR_UNSUPPORTED;
+    hipStream_t s = trx::api_stream(stream);
+    zc* gz = (zc*)ws;
+    double* Jy = (double*)((char*)ws + al256(sizeof(zc) * (size_t)batch * nx * ny));
+    const long per = (long)nx * ny;
+    int rc = dtype == TRX_C64 ? convert<float>(s, grid_is_complex, grid, batch, per, gz, nullptr, nullptr)
+                              : convert<double>(s, grid_is_complex, grid, batch, per, gz, nullptr, nullptr);
+    if (rc) return rc;
+    return field_core(s, gz, batch, nx, ny, sigma, hx, hy, nn, Jy);
+}
+
+extern "C" size_t trx_convmat_nv_ws_bytes(int dtype, int batch, int nx, int ny, int ox, int oy) {
+    if (batch <= 0 || ox < 0 || oy < 0 || nx <= 0 || ny <= 0) return 0;
+    return nv_layout(dtype, batch, nx, ny, ox, oy).total;
+}
+
+extern "C" int trx_convmat_nv(int dtype, int grid_is_complex, const void* grid, int batch, int nx, int ny, int ox, int oy, double sigma, double hx,
+                              double hy, const double* nn, void* Exx, void* Exy, void* Eyy, int* info, void* ws, size_t ws_bytes, void* stream) {
+    if (!grid || !Exx || !Exy || !Eyy || !info || !ws) return TRX_ERR_ARG;
+    if (batch <= 0 || ox < 0 || oy < 0 || nx <= 2 * ox || ny <= 2 * oy) return TRX_ERR_ARG;
+    if (!nn && !field_args_ok(batch, nx, ny, sigma, hx, hy)) return TRX_ERR_ARG;
+    if (dtype != TRX_C64 && dtype != TRX_C128) return TRX_ERR_DTYPE;
+    if (ws_bytes < trx_convmat_nv_ws_bytes(dtype, batch, nx, ny, ox, oy)) return TRX_ERR_WORKSPACE;
+    if (nx > 2048 || ny > 2048 || (!nn && sigma > NV_SIGMA_MAX)) return TRX_ERR_UNSUPPORTED;
+    hipStream_t s = trx::api_stream(stream);
+    if (dtype == TRX_C64)
+        return convmat_nv_t<float>(grid_is_complex, grid, batch, nx, ny, ox, oy, sigma, hx, hy, nn, Exx, Exy, Eyy, info, (char*)ws, dtype, s);
+    return convmat_nv_t<double>(grid_is_complex, grid, batch, nx, ny, ox, oy, sigma, hx, hy, nn, Exx, Exy, Eyy, info, (char*)ws, dtype, s);
+}
+
+extern "C" int trx_build_pq_tensor(int dtype, const void* Exx, const void* Exy, const void* Eyy, const void* Einv, const void* Mu,
+                                   const void* Muinv, const void* kx, const void* ky, int N, int batch, void* P, void* Q, void* stream) {
+    if (!Exx || !Exy || !Eyy || !Einv || !Mu || !Muinv || !kx || !ky || !P || !Q || N <= 0 || batch <= 0) return TRX_ERR_ARG;
+    hipStream_t s = trx::api_stream(stream);
+    const dim3 g(cdiv_i(N, 256), N, batch), blk(256);
+    if (dtype == TRX_C64)
+        TRX_LAUNCH((build_pq_tensor_kernel<float>), g, blk, 0, s, (const cx<float>*)Exx, (const cx<float>*)Exy, (const cx<float>*)Eyy,
+                   (const cx<float>*)Einv, (const cx<float>*)Mu, (const cx<float>*)Muinv, (const cx<float>*)kx, (const cx<float>*)ky, N,
+                   (cx<float>*)P, (cx<float>*)Q);
+    else if (dtype == TRX_C128)
+        TRX_LAUNCH((build_pq_tensor_kernel<double>), g, blk, 0, s, (const cx<double>*)Exx, (const cx<double>*)Exy, (const cx<double>*)Eyy,
+                   (const cx<double>*)Einv, (const cx<double>*)Mu, (const cx<double>*)Muinv, (const cx<double>*)kx, (const cx<double>*)ky, N,
+                   (cx<double>*)P, (cx<double>*)Q);
+    else
+        return TRX_ERR_DTYPE;
+    TRX_CHECK_LAUNCH();
+    return TRX_OK;
+}
+
+extern "C" size_t trx_build_a_tensor_ws_bytes(int dtype, int N, int batch) {
+    return (size_t)(dtype == TRX_C128 ? 16 : 8) * 4 * (size_t)batch * N * N;
+}
+
+extern "C" int trx_build_a_tensor(int dtype, const void* Exx, const void* Exy, const void* Eyy, const void* Einv, const void* mu, const void* kx,
+                                  const void* ky, int N, int batch, void* A, void* ws, size_t ws_bytes, void* stream) {
+    if (!Exx || !Exy || !Eyy || !Einv || !mu || !kx || !ky || !A || !ws || N <= 0 || batch <= 0) return TRX_ERR_ARG;
+    if (ws_bytes < trx_build_a_tensor_ws_bytes(dtype, N, batch)) return TRX_ERR_WORKSPACE;
+    hipStream_t s = trx::api_stream(stream);
+    if (dtype == TRX_C64)
+        return build_a_tensor_t<float>(s, (const cx<float>*)Exx, (const cx<float>*)Exy, (const cx<float>*)Eyy, (const cx<float>*)Einv,
+                                       (const cx<float>*)mu, (const cx<float>*)kx, (const cx<float>*)ky, N, batch, (cx<float>*)A, (cx<float>*)ws);
+    if (dtype == TRX_C128)
+        return build_a_tensor_t<double>(s, (const cx<double>*)Exx, (const cx<double>*)Exy, (const cx<double>*)Eyy, (const cx<double>*)Einv,
+                                        (const cx<double>*)mu, (const cx<double>*)kx, (const cx<double>*)ky, N, batch, (cx<double>*)A,
+                                        (cx<double>*)ws);
+    return TRX_ERR_DTYPE;
+}

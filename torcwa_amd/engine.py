@@ -159,6 +159,47 @@ class Engine:
         self._info(info, "convmat_li (1: zero grid value, 2: singular Toeplitz block)")
         return Ex, Ey, Ux, Uy
 
+    @_phase("assembly (convolution matrices, E^-1, A = PQ)")
+    def normal_field(self, grid, sigma, hx=1.0, hy=1.0):
+        """[B,nx,ny] grid -> [B,3,nx,ny] float64 products (Nx^2, Nx Ny, Ny^2) of the normal-vector field derived from the grid
+        (include/trx.h: trx_normal_field; sigma in cells, hx / hy the grid spacings)."""
+        B, nx, ny = grid.shape
+        cplx = grid.is_complex()
+        dt = grid.dtype if grid.dtype in (torch.float32, torch.complex64) else (torch.complex128 if cplx else torch.float64)
+        grid = self._c(grid.to(dt))
+        code = _lib.C64 if dt in (torch.float32, torch.complex64) else _lib.C128
+        nn = torch.empty((B, 3, nx, ny), dtype=torch.float64, device=self.device)
+        nws = self.lib.normal_field_ws_bytes(code, B, nx, ny)
+        ws = self._ws(nws)
+        self.lib.check(self.lib.normal_field(code, int(cplx), grid.data_ptr(), B, nx, ny, float(sigma), float(hx), float(hy), nn.data_ptr(),
+                                             ws.data_ptr(), nws, self.stream))
+        return nn
+
+    @_phase("assembly (convolution matrices, E^-1, A = PQ)")
+    def convmat_nv(self, grid, ox, oy, dtype, *, sigma=None, hx=1.0, hy=1.0, nn=None):
+        """[B,nx,ny] grid -> (Exx, Exy, Eyy) [B,N,N], the normal-vector tensor of convolution matrices (include/trx.h: trx_convmat_nv).
+        nn: [B,3,nx,ny] float64 product grids of a caller-supplied field, or None to derive the field from the grid with blur `sigma`."""
+        B, nx, ny = grid.shape
+        cplx = grid.is_complex()
+        grid = self._c(grid.to(dtype if cplx else _REAL[dtype]))
+        N = (2 * ox + 1) * (2 * oy + 1)
+        Exx = torch.empty((B, N, N), dtype=dtype, device=self.device)
+        Exy, Eyy = torch.empty_like(Exx), torch.empty_like(Exx)
+        if nn is not None:
+            nn = self._c(nn.to(device=self.device, dtype=torch.float64))
+            if tuple(nn.shape) != (B, 3, nx, ny):
+                raise ValueError(f"normal-field products must be [{B}, 3, {nx}, {ny}], got {list(nn.shape)}")
+        elif sigma is None:
+            raise ValueError("convmat_nv needs sigma when no field is supplied")
+        info = self._ints(B)
+        nws = self.lib.convmat_nv_ws_bytes(_CODE[dtype], B, nx, ny, ox, oy)
+        ws = self._ws(nws)
+        self.lib.check(self.lib.convmat_nv(_CODE[dtype], int(cplx), grid.data_ptr(), B, nx, ny, ox, oy, float(sigma or 0.0), float(hx), float(hy),
+                                           nn.data_ptr() if nn is not None else None, Exx.data_ptr(), Exy.data_ptr(), Eyy.data_ptr(),
+                                           info.data_ptr(), ws.data_ptr(), nws, self.stream))
+        self._info(info, "convmat_nv (1: zero grid value, 2: singular [1/eps])")
+        return Exx, Exy, Eyy
+
     # -- dense blocks ----------------------------------------------------------------------------------
     def gemm(self, A, Bm, *, opA=0, opB=0, alpha=1.0, beta=0.0, out=None):
         """Batched C = alpha op(A) op(B) + beta C for contiguous [B,*,*] operands."""
@@ -392,6 +433,31 @@ class Engine:
         ops = [self._c(t) for t in (Ex, Ey, Einv, mu.to(dt), kx, ky)]
         self._check(*ops)
         self.lib.check(self.lib.build_a_aniso(_CODE[dt], *[t.data_ptr() for t in ops], N, B, A.data_ptr(), ws.data_ptr(), nws, self.stream))
+        return A
+
+    @_phase("assembly (convolution matrices, E^-1, A = PQ)")
+    def build_pq_tensor(self, Exx, Exy, Eyy, Einv, M, Minv, kx, ky):
+        """P, Q with the in-plane permittivity tensor (normal-vector rule; include/trx.h: trx_build_pq_tensor)."""
+        B, N, _ = Exx.shape
+        dt = Exx.dtype
+        P = torch.empty((B, 2 * N, 2 * N), dtype=dt, device=self.device)
+        Q = torch.empty_like(P)
+        ops = [self._c(t) for t in (Exx, Exy, Eyy, Einv, M, Minv, kx, ky)]
+        self._check(*ops)
+        self.lib.check(self.lib.build_pq_tensor(_CODE[dt], *[t.data_ptr() for t in ops], N, B, P.data_ptr(), Q.data_ptr(), self.stream))
+        return P, Q
+
+    @_phase("assembly (convolution matrices, E^-1, A = PQ)")
+    def build_a_tensor(self, Exx, Exy, Eyy, Einv, mu, kx, ky):
+        """A = P Q for homogeneous mu [B] with the in-plane tensor (one N x 2N GEMM; include/trx.h: trx_build_a_tensor)."""
+        B, N, _ = Exx.shape
+        dt = Exx.dtype
+        A = torch.empty((B, 2 * N, 2 * N), dtype=dt, device=self.device)
+        nws = self.lib.build_a_tensor_ws_bytes(_CODE[dt], N, B)
+        ws = self._ws(nws)
+        ops = [self._c(t) for t in (Exx, Exy, Eyy, Einv, mu.to(dt), kx, ky)]
+        self._check(*ops)
+        self.lib.check(self.lib.build_a_tensor(_CODE[dt], *[t.data_ptr() for t in ops], N, B, A.data_ptr(), ws.data_ptr(), nws, self.stream))
         return A
 
 

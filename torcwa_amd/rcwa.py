@@ -6,7 +6,7 @@ libtrx kernels behind include/trx.h).  Attributes are exposed un-batched and in 
 """
 import torch
 
-from .batched import BatchedRCWA, PI_REF
+from .batched import BatchedRCWA, NV_SIGMA_DEFAULT, PI_REF
 from .fields import FieldMixin
 
 pi = PI_REF
@@ -14,12 +14,15 @@ pi = PI_REF
 
 class rcwa(FieldMixin):
     def __init__(self, freq, order, L, *, dtype=torch.complex64, device=None, stable_eig_grad=True,
-                 avoid_Pinv_instability=False, max_Pinv_instability=0.005, precision="high", engine=None, fourier_rule="laurent"):
+                 avoid_Pinv_instability=False, max_Pinv_instability=0.005, precision="high", engine=None, fourier_rule="laurent",
+                 nv_sigma=NV_SIGMA_DEFAULT):
         # fourier_rule (extension, keyword-only): "laurent" (the reference's factorisation) or "li" (Li's inverse rule for the in-plane
-        # field components of every patterned layer; faster convergence in the order for high-contrast gratings)
+        # field components of every patterned layer; faster convergence in the order for high-contrast gratings) or "normal"
+        # (the normal-vector method for curved / oblique boundaries; field smoothed over nv_sigma grid cells, or add_layer(normal_field=...))
         self._b = BatchedRCWA(freq, order, L, batch=1, dtype=dtype, device=device, stable_eig_grad=stable_eig_grad,
                               avoid_Pinv_instability=avoid_Pinv_instability, max_Pinv_instability=max_Pinv_instability,
-                              precision=precision, engine=engine, fourier_rule=fourier_rule)
+                              precision=precision, engine=engine, fourier_rule=fourier_rule,
+                              nv_sigma=nv_sigma)
         self._dtype = self._b._dtype
         self._device = self._b._device
         self.freq = torch.as_tensor(freq, dtype=self._dtype, device=self._device)      # rcwa.py:60
@@ -47,7 +50,8 @@ class rcwa(FieldMixin):
         if hasattr(self, "Sout"):
             self.Sout = [self._u(b.dense()) for b in self._b._Sout]
 
-    def add_layer(self, thickness, eps=1., mu=1.):
+    def add_layer(self, thickness, eps=1., mu=1., normal_field=None):
+        # normal_field (extension, fourier_rule="normal" only): (Nx, Ny) grids of a caller-supplied in-plane field (BatchedRCWA.add_layer)
         def prep(v):
             if isinstance(v, (float, complex)):
                 return v
@@ -55,7 +59,7 @@ class rcwa(FieldMixin):
             if v.dim() == 0 or (v.dim() == 1 and v.shape[0] == 1):
                 return v.reshape(1)
             return v
-        self._b.add_layer(thickness, prep(eps), prep(mu))
+        self._b.add_layer(thickness, prep(eps), prep(mu), normal_field=normal_field)
 
     def solve_global_smatrix(self):
         self._b.solve_global_smatrix()
@@ -142,6 +146,9 @@ class rcwa(FieldMixin):
     eps_conv = property(lambda self: self._ul(self._b.eps_conv))
     eps_conv_x = property(lambda self: self._ul(self._b.eps_conv_x))
     eps_conv_y = property(lambda self: self._ul(self._b.eps_conv_y))
+    eps_conv_xx = property(lambda self: self._ul(self._b.eps_conv_xx))
+    eps_conv_xy = property(lambda self: self._ul(self._b.eps_conv_xy))
+    eps_conv_yy = property(lambda self: self._ul(self._b.eps_conv_yy))
     mu_conv = property(lambda self: self._ul(self._b.mu_conv))
     P = property(lambda self: self._ul(self._b.P))
     Q = property(lambda self: self._ul(self._b.Q))

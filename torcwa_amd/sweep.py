@@ -12,7 +12,7 @@ import os
 import numpy as np
 import torch
 
-from .batched import BatchedRCWA
+from .batched import NV_SIGMA_DEFAULT, BatchedRCWA, check_fourier_rule
 
 _DATA = os.path.join(os.path.dirname(os.path.abspath(__file__)), "data")
 
@@ -77,10 +77,10 @@ def rectangle_density(nx, ny, Lx, Ly, Wx, Wy, Cx, Cy, theta=0.0, edge_sharpness=
 
 
 def _solve_chunk(freq, layers, order, L, eps_in, eps_out, inc_ang, azi_ang, dtype, precision, engine, orders,
-                 polarization, direction, port, check_info, eig_route="auto", route_hint=None, fourier_rule="laurent"):
+                 polarization, direction, port, check_info, eig_route="auto", route_hint=None, fourier_rule="laurent", nv_sigma=NV_SIGMA_DEFAULT):
     """layers: list of (thickness, eps[, mu]); thickness scalar or [b]; eps/mu scalar, [b] or [b,nx,ny]."""
     sim = BatchedRCWA(freq, order, L, dtype=dtype, precision=precision, engine=engine, keep_coupling=False, fold_layers=True,
-                      eig_route=eig_route, route_hint=route_hint, fourier_rule=fourier_rule)
+                      eig_route=eig_route, route_hint=route_hint, fourier_rule=fourier_rule, nv_sigma=nv_sigma)
     if eps_in is not None:
         sim.add_input_layer(eps=eps_in)
     if eps_out is not None:
@@ -98,6 +98,9 @@ def _solve_chunk(freq, layers, order, L, eps_in, eps_out, inc_ang, azi_ang, dtyp
 _POINT_MATRICES = {1: 15.0, 2: 18.0}          # layers == 1 / layers >= 2 (what the allocator RESERVES, which is what must fit)
 # fourier_rule="li": Ex and Ey (two N x N = n^2 / 4 matrices each) live next to E, E^-1 and the assembly workspace until A exists
 _LI_EXTRA = 0.5
+# fourier_rule="normal": Exx, Exy, Eyy (three N x N) next to E, E^-1 while A is built, and inside trx_convmat_nv the workspace ([1/eps], its
+# inverse's workspace and the three product matrices: five more N x N) -- 8 N^2 = 2 n^2
+_NV_EXTRA = 2.0
 _HEADROOM = 0.10                               # fraction of the device memory a sweep leaves free
 
 
@@ -111,7 +114,7 @@ def auto_chunk(B, order, n_layers, precision, device, dtype=torch.complex64, str
     # element size of the COMPUTE dtype: complex128 unless a complex64 problem is solved natively (BatchedRCWA: precision="native" only
     # halves the element of complex64 problems); `streams` chunks are resident at once when the sweep is dealt to several streams
     elem = 8 if (precision == "native" and dtype == torch.complex64) else 16
-    mats = _POINT_MATRICES[1 if n_layers <= 1 else 2] + (_LI_EXTRA if fourier_rule == "li" else 0.0)
+    mats = _POINT_MATRICES[1 if n_layers <= 1 else 2] + {"li": _LI_EXTRA, "normal": _NV_EXTRA}.get(fourier_rule, 0.0)
     per_point = mats * n * n * elem * max(1, int(streams))
     free, total = torch.cuda.mem_get_info(device)
     free += torch.cuda.memory_reserved(device) - torch.cuda.memory_allocated(device)      # the caching allocator's idle blocks are ours to reuse
@@ -136,7 +139,8 @@ def _slice(v, lo, hi, B):
 
 def solve_stack_sweep(freq, layers, order, L, *, eps_in=None, eps_out=None, inc_ang=0.0, azi_ang=0.0, dtype=torch.complex64,
                       precision="high", engine=None, chunk=None, streams=1, orders=((0, 0),), polarization="xx",
-                      direction="forward", port="transmission", check_info=True, eig_route="auto", fourier_rule="laurent"):
+                      direction="forward", port="transmission", check_info=True, eig_route="auto", fourier_rule="laurent",
+                      nv_sigma=NV_SIGMA_DEFAULT):
     """B sweep points of a multi-layer stack (BASELINE.json configs 2-4): the reference's per-point Python loop
     (example/Example1-1.ipynb, Example3.ipynb) as chunks of a batched solve.  `layers` as in `_solve_chunk`, with
     per-point quantities carrying a leading dimension B = len(freq).  Returns the requested S-parameter [B, len(orders)].
@@ -144,10 +148,10 @@ def solve_stack_sweep(freq, layers, order, L, *, eps_in=None, eps_out=None, inc_
     eig_route: "auto" (mixed-precision eigensolver; once a chunk of THIS call had to redo matrices in fp64, the remaining layers and chunks
     of this call use the all-fp64 route -- BatchedRCWA._eig_call), "mixed" or "fp64".
 
-    fourier_rule: "laurent" (default) or "li" (Li's inverse rule in every patterned layer, BatchedRCWA)."""
+    fourier_rule: "laurent" (default), "li" (Li's inverse rule in every patterned layer, BatchedRCWA) or "normal" (the normal-vector method,
+    the field derived from each grid with a Gaussian of nv_sigma cells)."""
     from .engine import default_engine
-    if fourier_rule not in ("laurent", "li"):
-        raise ValueError(f"fourier_rule must be 'laurent' or 'li', got {fourier_rule!r}")
+    check_fourier_rule(fourier_rule)
     B = freq.shape[0]
     eng = engine if engine is not None else default_engine()
     old_check, eng.check_info = eng.check_info, check_info         # restored below: the engine may be shared with other solvers
@@ -165,7 +169,7 @@ def solve_stack_sweep(freq, layers, order, L, *, eps_in=None, eps_out=None, inc_
         lays = [tuple(_slice(v, lo, hi, B) for v in lay) for lay in layers]
         outs[i] = _solve_chunk(freq[lo:hi], lays, order, L, _slice(eps_in, lo, hi, B), _slice(eps_out, lo, hi, B), _slice(inc_ang, lo, hi, B),
                                _slice(azi_ang, lo, hi, B), dtype, precision, engine, orders, polarization, direction, port, check_info,
-                               eig_route=eig_route, route_hint=route_hint, fourier_rule=fourier_rule)
+                               eig_route=eig_route, route_hint=route_hint, fourier_rule=fourier_rule, nv_sigma=nv_sigma)
 
     dev = freq.device
     try:
@@ -207,7 +211,7 @@ def _run_spans(run, spans, streams, dev):
 
 def solve_single_layer_sweep(freq, eps_grids, thickness, order, L, **kw):
     """B sweep points of a 1-patterned-layer stack (configs 2 and 4 of BASELINE.json): freq [B], eps_grids [B,nx,ny].  Keywords as
-    solve_stack_sweep (fourier_rule="li": Li's inverse rule).
+    solve_stack_sweep (fourier_rule="li": Li's inverse rule; "normal": the normal-vector method, nv_sigma).
 
     chunk   : points solved in lock-step by one batched solver (bounds the HBM footprint; default None = as many as the free HBM holds with
               10 % headroom, `auto_chunk`).  At order [15,15] (n = 1922) a point costs about 0.6 GB allocated / 0.9 GB reserved, so about 256 points
