@@ -51,6 +51,16 @@ size_t trx_convmat_ws_bytes(int dtype, int batch, int nx, int ny, int ox, int oy
 int trx_convmat(int dtype, int grid_is_complex, const void* grid, int batch, int nx, int ny, int ox, int oy,
                 void* out, void* ws, size_t ws_bytes, void* stream);
 
+/* ---- Fourier factorisation for an arbitrary order set (oblique lattices, circular truncation; no reference counterpart) ---------------
+ * out[b,i,j] = c[b, m_i-m_j, n_i-n_j],  c = DFT2(grid[b]) / (n1*n2),  (m_i, n_i) = mn[i]: a device int32 [N,2] list of harmonic indices in
+ * the lattice basis (grid axis 0 along a1, axis 1 along a2), in the caller's order.  The coefficients are those of trx_convmat over the box
+ * |p| <= 2 mmax, |q| <= 2 nmax (same pruned fp64 DFT), so mn = the x-major rectangle of (ox, oy) with mmax = ox, nmax = oy gives trx_convmat's
+ * output bit for bit.  Requires n1 > 2*mmax, n2 > 2*nmax and |m_i| <= mmax, |n_i| <= nmax (else TRX_ERR_ARG; the list is checked on the host,
+ * one synchronisation of `stream`); max(n1, n2) <= 2048 as trx_convmat. */
+size_t trx_convmat_orders_ws_bytes(int dtype, int batch, int n1, int n2, int N, int mmax, int nmax);
+int trx_convmat_orders(int dtype, int grid_is_complex, const void* grid, int batch, int n1, int n2, const int* mn, int N, int mmax, int nmax,
+                       void* out, void* ws, size_t ws_bytes, void* stream);
+
 /* ---- Fourier factorisation, Li's inverse rule (no reference counterpart: the reference has Laurent's rule only) ---------------------
  * L. Li, JOSA A 13, 1870 (1996); 14, 2758 (1997).  For each grid[b] ([nx, ny], layout and index map as trx_convmat):
  *   Ex[(m,n),(m',n')] = F[m,m',n-n'],  F[m,m',q] = (1/ny) sum_y Uy[y][m,m'] e^{-2 pi i q y/ny},  Uy[y] = Toeplitz_x(1/grid[:,y])^-1
@@ -88,6 +98,18 @@ int trx_normal_field(int dtype, int grid_is_complex, const void* grid, int batch
 size_t trx_convmat_nv_ws_bytes(int dtype, int batch, int nx, int ny, int ox, int oy);
 int trx_convmat_nv(int dtype, int grid_is_complex, const void* grid, int batch, int nx, int ny, int ox, int oy, double sigma, double hx, double hy,
                    const double* nn, void* Exx, void* Exy, void* Eyy, int* info, void* ws, size_t ws_bytes, void* stream);
+/* On an oblique lattice with an arbitrary order set.  h: HOST double[4], the row-major cell matrix whose rows are a1/n1 and a2/n2 (grid axis 0
+ * along a1, axis 1 along a2).  The physical gradient is h^-1 (du g, dv g) of the periodic central differences du, dv in index units; the blur
+ * stays in index space (on a skewed cell it is anisotropic in physical units).  A diagonal h with positive entries is trx_normal_field with
+ * hx = h[0], hy = h[3], bit for bit.  trx_normal_field_lattice takes the workspace of trx_normal_field_ws_bytes.
+ * trx_convmat_nv_orders: trx_convmat_nv with the [eps], [1/eps] and product matrices of trx_convmat_orders (mn, N, mmax, nmax as there) and
+ * the field of trx_normal_field_lattice (h is ignored when nn is given).  Same outputs, info and arithmetic; N x N outputs. */
+int trx_normal_field_lattice(int dtype, int grid_is_complex, const void* grid, int batch, int n1, int n2, double sigma, const double* h, double* nn,
+                             void* ws, size_t ws_bytes, void* stream);
+size_t trx_convmat_nv_orders_ws_bytes(int dtype, int batch, int n1, int n2, int N, int mmax, int nmax);
+int trx_convmat_nv_orders(int dtype, int grid_is_complex, const void* grid, int batch, int n1, int n2, const int* mn, int N, int mmax, int nmax,
+                          double sigma, const double* h, const double* nn, void* Exx, void* Exy, void* Eyy, int* info, void* ws, size_t ws_bytes,
+                          void* stream);
 
 /* ---- dense complex building blocks (the torch.matmul / torch.linalg.inv call sites, rcwa.py:1157-1304) -------- */
 /* C = alpha*op(A)*op(B) + beta*C, batched with element strides; alpha/beta point to HOST complex scalars. */

@@ -19,6 +19,9 @@ _SIGS = {
     "trx_strerror": (c_char_p, [c_int]),
     "trx_convmat_ws_bytes": (c_size_t, [c_int, c_int, c_int, c_int, c_int, c_int]),
     "trx_convmat": (c_int, [c_int, c_int, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "trx_convmat_orders_ws_bytes": (c_size_t, [c_int, c_int, c_int, c_int, c_int, c_int, c_int]),
+    "trx_convmat_orders": (c_int, [c_int, c_int, c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_size_t,
+                                   c_void_p]),
     "trx_convmat_li_ws_bytes": (c_size_t, [c_int, c_int, c_int, c_int, c_int, c_int]),
     "trx_convmat_li": (c_int, [c_int, c_int, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                c_void_p, c_size_t, c_void_p]),
@@ -32,6 +35,10 @@ _SIGS = {
     "trx_convmat_nv_ws_bytes": (c_size_t, [c_int, c_int, c_int, c_int, c_int, c_int]),
     "trx_convmat_nv": (c_int, [c_int, c_int, c_void_p, c_int, c_int, c_int, c_int, c_int, c_double, c_double, c_double, c_void_p, c_void_p, c_void_p,
                                c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "trx_normal_field_lattice": (c_int, [c_int, c_int, c_void_p, c_int, c_int, c_int, c_double, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "trx_convmat_nv_orders_ws_bytes": (c_size_t, [c_int, c_int, c_int, c_int, c_int, c_int, c_int]),
+    "trx_convmat_nv_orders": (c_int, [c_int, c_int, c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_int, c_int, c_double, c_void_p, c_void_p,
+                                      c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "trx_build_pq_tensor": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p,
                                     c_void_p, c_void_p]),
     "trx_build_a_tensor_ws_bytes": (c_size_t, [c_int, c_int, c_int]),

@@ -45,6 +45,41 @@ class ConvMatFn(torch.autograd.Function):
         return g.to(gdt), None, None, None, None
 
 
+class ConvMatOrdersFn(torch.autograd.Function):
+    """E = convmat_orders(grid, mn) (include/trx.h: trx_convmat_orders) for an [N,2] harmonic list.  The backward mirrors ConvMatFn: the
+    scatter-add of grad_E over the differences (m_i - m_j, n_i - n_j), then the conjugate pruned DFT over the coefficient box."""
+
+    @staticmethod
+    def forward(ctx, grid, mn, cdtype, engine):
+        mn = torch.as_tensor(mn)
+        ctx.meta = (mn, grid.shape, grid.is_complex(), grid.dtype)
+        return engine.convmat_orders(grid, mn, cdtype)
+
+    @staticmethod
+    def backward(ctx, gE):
+        mn, (B, n1, n2), cplx, gdt = ctx.meta
+        dev = gE.device
+        mn = mn.to(device=dev, dtype=torch.int64)
+        mmax, nmax = (int(v) for v in mn.abs().amax(dim=0).cpu())
+        nq = 4 * nmax + 1
+        dm = (mn[:, None, 0] - mn[None, :, 0] + 2 * mmax).reshape(-1)
+        dn = (mn[:, None, 1] - mn[None, :, 1] + 2 * nmax).reshape(-1)
+        G = torch.zeros((B, (4 * mmax + 1) * nq), dtype=gE.dtype, device=dev)
+        G.index_add_(1, dm * nq + dn, gE.reshape(B, -1))                    # G[p,q] = sum_{(i,j): diff = (p,q)} gE[i,j]
+        G = G.reshape(B, 4 * mmax + 1, nq)
+        rdt = torch.float64 if gE.dtype == torch.complex128 else torch.float32
+        x = torch.arange(n1, device=dev, dtype=rdt)[:, None]
+        p = torch.arange(-2 * mmax, 2 * mmax + 1, device=dev, dtype=rdt)[None, :]
+        y = torch.arange(n2, device=dev, dtype=rdt)[None, :]
+        q = torch.arange(-2 * nmax, 2 * nmax + 1, device=dev, dtype=rdt)[:, None]
+        Fx = torch.exp(2j * math.pi * (x * p) / n1).to(gE.dtype)             # conj of the forward twiddle
+        Fy = torch.exp(2j * math.pi * (q * y) / n2).to(gE.dtype)
+        g = (Fx[None] @ G @ Fy[None]) / (n1 * n2)                            # [B, n1, n2]
+        if not cplx:
+            g = torch.real(g)
+        return g.to(gdt), None, None, None
+
+
 def _twiddle(n, o, dev):
     """[n, 4o+1] complex128: exp(+2 pi i (q-2o) r / n) with exact integer phase reduction (the conjugate of the forward twiddle)."""
     r = torch.arange(n, device=dev, dtype=torch.int64)[:, None]

@@ -9,10 +9,12 @@ All per-point scalars (`freq`, angles, homogeneous eps/mu, thickness) may be pyt
 """
 import warnings
 
+import numpy as np
 import torch
 
 from .engine import Engine, default_engine
 from . import autograd_ops as ag
+from . import lattice as _lat
 from .torch_eig import Eig
 
 # torcwa/rcwa.py:5 -- the reference's pi (typo in the 9th decimal) is part of its observable behaviour
@@ -82,6 +84,7 @@ class BatchedRCWA:
                  avoid_Pinv_instability=False, max_Pinv_instability=0.005, precision="high", engine=None,
                  keep_coupling=True, fold_layers=False, eig_route="auto", route_hint=None, fourier_rule="laurent", nv_sigma=NV_SIGMA_DEFAULT):
         check_fourier_rule(fourier_rule)
+        # fourier_rule="li" needs the rectangular order box on a rectangular lattice (ValueError otherwise, see the order / lattice below).
         # fourier_rule="li": Li's inverse rule for the x / y components of D in every patterned layer (Ex, Ey convolution matrices,
         # include/trx.h trx_convmat_li); Ez / Hz keep Laurent's matrices (E^-1 in P, trx_hmodes, eps_conv).  "laurent": the reference's rule.
         # fourier_rule="normal": the normal-vector method (in-plane tensor Exx, Exy, Eyy of the permittivity, trx_convmat_nv) with the field
@@ -122,13 +125,46 @@ class BatchedRCWA:
         self.B = int(batch)
         self.freq = self._bvec(freq)                                                    # [B] complex
         self.omega = (2 * PI_REF) * torch.real(self.freq)                               # rcwa.py:61  [B] real
-        self.order = [int(order[0]), int(order[1])]
-        self.order_x = torch.arange(-self.order[0], self.order[0] + 1, dtype=torch.int64, device=self._device)
-        self.order_y = torch.arange(-self.order[1], self.order[1] + 1, dtype=torch.int64, device=self._device)
-        self.order_N = len(self.order_x) * len(self.order_y)
+        # L: [Lx, Ly] or a 2 x 2 array of lattice vectors (rows a1, a2); order: [ox, oy] or an [N, 2] list of harmonics (m, n) in the lattice
+        # basis (torcwa_amd.lattice).  [ox, oy] on a rectangular lattice is the reference's path, unchanged; anything else is the general path:
+        # an order list, the convolution matrices of trx_convmat_orders, G_norm = (b1, b2) / f, and order_x / order_y / Gx_norm / Gy_norm None.
+        kind, box, mn = _lat.parse_order(order)
+        A = _lat.lattice_matrix(L)
+        rect_lattice = _lat.is_rectangular(A)
+        flat_L = _lat._host(L).shape == (2,)
+        Lx, Ly = (L[0], L[1]) if flat_L else ((L[0][0], L[1][1]) if rect_lattice else (None, None))
+        self._general = kind == "list" or not rect_lattice
         self.L = L
-        self.Gx_norm = 1 / (L[0] * self.freq)                                           # rcwa.py:72
-        self.Gy_norm = 1 / (L[1] * self.freq)
+        self._lattice = A
+        self._Lxy = (Lx, Ly)          # the rectangle's periods (None, None on an oblique lattice), whichever form L took
+        if not self._general:
+            self.order = [int(box[0]), int(box[1])]
+            self.order_x = torch.arange(-self.order[0], self.order[0] + 1, dtype=torch.int64, device=self._device)
+            self.order_y = torch.arange(-self.order[1], self.order[1] + 1, dtype=torch.int64, device=self._device)
+            self.order_N = len(self.order_x) * len(self.order_y)
+            self.Gx_norm = 1 / (Lx * self.freq)                                         # rcwa.py:72
+            self.Gy_norm = 1 / (Ly * self.freq)
+            mn = _lat.rect_orders(*self.order)
+            G = torch.zeros((self.B, 2, 2), dtype=self.Gx_norm.dtype, device=self._device)
+            G[:, 0, 0], G[:, 1, 1] = self.Gx_norm, self.Gy_norm
+        else:
+            if self.fourier_rule == "li":
+                raise ValueError('fourier_rule="li" needs the rectangular order box [ox, oy] on a rectangular lattice')
+            if kind == "rect":
+                mn = _lat.rect_orders(*box)
+            self.order = self.order_x = self.order_y = self.Gx_norm = self.Gy_norm = None
+            self.order_N = int(mn.shape[0])
+            if rect_lattice:          # a diagonal lattice keeps the reference's expression: kx, ky bit-identical to the rectangular path
+                G = torch.zeros((self.B, 2, 2), dtype=self._cdtype, device=self._device)
+                G[:, 0, 0], G[:, 1, 1] = 1 / (Lx * self.freq), 1 / (Ly * self.freq)
+            else:
+                G = torch.as_tensor(_lat.reciprocal(A), dtype=self._cdtype, device=self._device)[None] / self.freq[:, None, None]
+        self.G_norm = G                                                                 # [B, 2, 2]: rows b1 / f, b2 / f
+        self.orders = torch.as_tensor(mn, dtype=torch.int64, device=self._device)       # [N, 2] (m, n) of every harmonic, in matrix order
+        self._mn = mn
+        self._mn_dev = self.orders.to(torch.int32).contiguous()
+        self._mmax, self._nmax = int(np.abs(mn[:, 0]).max()), int(np.abs(mn[:, 1]).max())
+        self._index = {(int(p), int(q)): i for i, (p, q) in enumerate(mn)} if self._general else None
         one = torch.ones(self.B, dtype=self._cdtype, device=self._device)
         self.eps_in, self.mu_in, self.eps_out, self.mu_out = one, one.clone(), one.clone(), one.clone()
         self.has_in = self.has_out = False
@@ -182,11 +218,17 @@ class BatchedRCWA:
         nref = torch.real(torch.sqrt(em))
         self.kx0_norm = nref * torch.sin(self.inc_ang) * torch.cos(self.azi_ang)
         self.ky0_norm = nref * torch.sin(self.inc_ang) * torch.sin(self.azi_ang)
-        kx = self.kx0_norm[:, None] + self.order_x[None, :] * self.Gx_norm[:, None]     # [B, 2ox+1]
-        ky = self.ky0_norm[:, None] + self.order_y[None, :] * self.Gy_norm[:, None]     # [B, 2oy+1]
-        self.kx_norm, self.ky_norm = kx, ky
-        self.Kx_norm_dn = kx[:, :, None].expand(-1, -1, ky.shape[1]).reshape(self.B, -1).contiguous()   # x-major
-        self.Ky_norm_dn = ky[:, None, :].expand(-1, kx.shape[1], -1).reshape(self.B, -1).contiguous()
+        if self._general:         # k = k0 + m b1 / f + n b2 / f per listed harmonic; kx_norm / ky_norm (the axes of a box) do not exist
+            m, n, G = self.orders[None, :, 0], self.orders[None, :, 1], self.G_norm
+            self.kx_norm = self.ky_norm = None
+            self.Kx_norm_dn = (self.kx0_norm[:, None] + m * G[:, 0, 0, None] + n * G[:, 1, 0, None]).contiguous()
+            self.Ky_norm_dn = (self.ky0_norm[:, None] + m * G[:, 0, 1, None] + n * G[:, 1, 1, None]).contiguous()
+        else:
+            kx = self.kx0_norm[:, None] + self.order_x[None, :] * self.Gx_norm[:, None]     # [B, 2ox+1]
+            ky = self.ky0_norm[:, None] + self.order_y[None, :] * self.Gy_norm[:, None]     # [B, 2oy+1]
+            self.kx_norm, self.ky_norm = kx, ky
+            self.Kx_norm_dn = kx[:, :, None].expand(-1, -1, ky.shape[1]).reshape(self.B, -1).contiguous()   # x-major
+            self.Ky_norm_dn = ky[:, None, :].expand(-1, kx.shape[1], -1).reshape(self.B, -1).contiguous()
         kxd, kyd = self.Kx_norm_dn, self.Ky_norm_dn
         self._Vf = _halfspace_V(kxd, kyd, 1.0)
         self._Vfinv = self._Vf.inv()
@@ -226,6 +268,10 @@ class BatchedRCWA:
             g = torch.as_tensor(v, device=self._device)
             if g.dim() == 2:
                 g = g[None].expand(B, -1, -1)
+            if self._general:
+                if diff:
+                    return ag.ConvMatOrdersFn.apply(g.contiguous(), self.orders, cdt, eng), None, None
+                return eng.convmat_orders(g.contiguous(), self._mn_dev, cdt, self._mmax, self._nmax), None, None
             if diff:
                 return ag.ConvMatFn.apply(g.contiguous(), self.order[0], self.order[1], cdt, eng), None, None
             C = eng.convmat(g.contiguous(), self.order[0], self.order[1], cdt)          # rcwa.py:1183-1204
@@ -249,6 +295,13 @@ class BatchedRCWA:
                 g = g[None].expand(B, -1, -1)
             g = g.contiguous()
             nn = self._nv_products(g, normal_field)
+            if self._general:
+                h = self._nv_spacing(g)
+                if diff:
+                    if nn is None:
+                        nn = eng.normal_field_lattice(g.detach(), self.nv_sigma, h)
+                    return self._nv_tensor_torch(g, nn)
+                return eng.convmat_nv_orders(g, self._mn_dev, cdt, sigma=self.nv_sigma, h=h, nn=nn, mmax=self._mmax, nmax=self._nmax)
             hx, hy = self._nv_spacing(g)
             if diff:
                 if nn is None:                 # the field derived from the grid is a constant of the differentiable path (detached)
@@ -389,8 +442,11 @@ class BatchedRCWA:
             lst.append(None)
 
     def _nv_spacing(self, g):
-        """Grid spacings (hx, hy) of a [B, nx, ny] grid over the unit cell: they orient the gradient of the normal-vector field."""
-        return float(self.L[0]) / g.shape[1], float(self.L[1]) / g.shape[2]
+        """Grid spacings (hx, hy) of a [B, nx, ny] grid over the unit cell: they orient the gradient of the normal-vector field.  On the
+        general path the cell matrix instead: [2, 2], rows a1 / n1 and a2 / n2 (include/trx.h: trx_normal_field_lattice)."""
+        if self._general:
+            return self._lattice / np.array([[g.shape[1]], [g.shape[2]]], dtype=np.float64)
+        return float(self._Lxy[0]) / g.shape[1], float(self._Lxy[1]) / g.shape[2]
 
     def _nv_products(self, g, normal_field):
         """[B,3,nx,ny] float64 (Nx^2, Nx Ny, Ny^2): from a caller-supplied field, or None (the library derives it from the grid)."""
@@ -406,11 +462,18 @@ class BatchedRCWA:
     def _nv_tensor_torch(self, g, nn):
         """(Exx, Exy, Eyy) from the differentiable primitives: ConvMatFn of eps and 1/eps, InverseFn, GemmFn (the symmetrised products
         (D C + C D) / 2 of include/trx.h: trx_convmat_nv); the field products nn are constants."""
-        eng, cdt, (ox, oy) = self.engine, self._cdtype, self.order
+        eng, cdt = self.engine, self._cdtype
         B = g.shape[0]
-        E = ag.ConvMatFn.apply(g, ox, oy, cdt, eng)
-        D = E - ag.InverseFn.apply(ag.ConvMatFn.apply((1 / g).contiguous(), ox, oy, cdt, eng), eng)
-        C = eng.convmat(nn.reshape(3 * B, *nn.shape[2:]), ox, oy, cdt).reshape(B, 3, E.shape[1], E.shape[2])
+        if self._general:         # ConvMatOrdersFn / convmat_orders of the order list in place of the rectangle's
+            conv_d = lambda x: ag.ConvMatOrdersFn.apply(x, self.orders, cdt, eng)
+            conv_c = lambda x: eng.convmat_orders(x, self._mn_dev, cdt, self._mmax, self._nmax)
+        else:
+            ox, oy = self.order
+            conv_d = lambda x: ag.ConvMatFn.apply(x, ox, oy, cdt, eng)
+            conv_c = lambda x: eng.convmat(x, ox, oy, cdt)
+        E = conv_d(g)
+        D = E - ag.InverseFn.apply(conv_d((1 / g).contiguous()), eng)
+        C = conv_c(nn.reshape(3 * B, *nn.shape[2:])).reshape(B, 3, E.shape[1], E.shape[2])
         DC = [0.5 * (ag.GemmFn.apply(D, C[:, c].contiguous(), eng) + ag.GemmFn.apply(C[:, c].contiguous(), D, eng)) for c in range(3)]
         return E - DC[0], -DC[1], E - DC[2]
 
@@ -650,6 +713,13 @@ class BatchedRCWA:
 
     # ---- a11 ---------------------------------------------------------------------------------------------
     def _matching_indices(self, orders):                                                # rcwa.py:1115-1122
+        if self._general:         # position in the order list; the reference's clamping into the box applies to the rectangular path only
+            idx = []
+            for p, q in orders.reshape(-1, 2).tolist():
+                if (p, q) not in self._index:
+                    raise ValueError(f"harmonic ({p}, {q}) is not in this solver's order set")
+                idx.append(self._index[(p, q)])
+            return torch.as_tensor(idx, dtype=torch.int64, device=orders.device)
         ox, oy = self.order
         orders[orders[:, 0] < -ox, 0] = -ox
         orders[orders[:, 0] > ox, 0] = ox

@@ -3,7 +3,7 @@
 
 using namespace trx;
 
-extern "C" int trx_version(void) { return 300; }   // 0.3.0: trx_normal_field, trx_convmat_nv, trx_build_pq_tensor, trx_build_a_tensor
+extern "C" int trx_version(void) { return 400; }   // 0.4.0: trx_convmat_orders, trx_normal_field_lattice, trx_convmat_nv_orders
 
 extern "C" const char* trx_strerror(int code) {
     switch (code) {

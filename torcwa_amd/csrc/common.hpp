@@ -198,5 +198,10 @@ int lu_solve(hipStream_t s, const cx<T>* LU, int lda, long sA, int n, const int*
 // X = B A^-1 in place on B [nrows x n] from the factors of lu_factor; idx: n ints per matrix of scratch (lu.hip)
 template <class T>
 int lu_solve_right(hipStream_t s, const cx<T>* LU, int lda, long sA, int n, const int* piv, cx<T>* B, int ldb, long sB, int nrows, int batch, int* idx);
+// order lists of trx_convmat_orders (convmat.hip): the host check of every |m_i| <= mmax, |n_i| <= nmax (one copy of the list and one
+// synchronisation of s), and the convolution matrix of a list already checked (arguments as trx_convmat_orders, validated by the caller)
+int orders_check(hipStream_t s, const int* mn, int N, int mmax, int nmax);
+int convmat_orders_checked(hipStream_t s, int dtype, int cplx, const void* grid, int batch, int n1, int n2, const int* mn, int N, int mmax,
+                           int nmax, void* out, void* ws);
 
 }  // namespace trx

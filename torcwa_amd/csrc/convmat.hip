@@ -5,6 +5,9 @@
 // a full nx x ny FFT the kernels evaluate a pruned, separable DFT directly (rows then columns), with exact integer
 // phase reduction ((dn*y) mod ny) and twiddles/accumulation in fp64 for both dtypes, then scatter the coefficients
 // into out[b,i,j] = c[b, m_i-m_j, n_i-n_j], i = (m+ox)(2oy+1)+(n+oy)  -- the same index map as rcwa.py:1187-1200.
+// trx_convmat_orders: the same coefficients gathered for an arbitrary list of harmonics (m_i, n_i) (oblique lattices, circular truncation).
+#include <vector>
+
 #include "common.hpp"
 
 namespace trx {
@@ -99,7 +102,75 @@ int convmat_t(int cplx, const void* grid, int batch, int nx, int ny, int ox, int
     TRX_CHECK_LAUNCH();
     return TRX_OK;
 }
+
+// ---- arbitrary order set (oblique lattices, circular truncation) -------------------------------------------------------------------------
+// out[b,i,j] = coef[b, m_i-m_j+2mmax, n_i-n_j+2nmax] for the caller's list mn[i] = (m_i, n_i).  One workgroup = ORD_ROWS consecutive rows i
+// of one batch entry; lanes run over j, so every store of a row is one coalesced segment.  The (4mmax+1)(4nmax+1) coefficient box of the
+// entry (61^2 x 16 B = 60 KB at mmax = nmax = 15) is staged in LDS once per workgroup when it fits (LDS), else read from global (L2-resident).
+constexpr int ORD_ROWS = 32;
+constexpr size_t ORD_LDS_MAX = 160 * 1024;
+
+template <class T, bool LDS>
+__global__ __launch_bounds__(256) void orders_gather_kernel(const zc* __restrict__ coef, const int* __restrict__ mn, int N, int mmax, int nmax,
+                                                            cx<T>* __restrict__ out) {
+    TRX_DYN_SMEM(smem);
+    zc* box = reinterpret_cast<zc*>(smem);
+    const int b = blockIdx.y;
+    const int np = 4 * mmax + 1, nq = 4 * nmax + 1;
+    const zc* cb = coef + (long)b * np * nq;
+    if (LDS) {
+        for (int e = threadIdx.x; e < np * nq; e += blockDim.x) box[e] = cb[e];
+        __syncthreads();
+    }
+    const int i0 = blockIdx.x * ORD_ROWS;
+    const int i1 = i0 + ORD_ROWS < N ? i0 + ORD_ROWS : N;
+    for (int j = threadIdx.x; j < N; j += blockDim.x) {
+        const int cj = (2 * mmax - mn[2 * j]) * nq + (2 * nmax - mn[2 * j + 1]);
+        for (int i = i0; i < i1; ++i) {
+            const int e = cj + mn[2 * i] * nq + mn[2 * i + 1];       // (m_i - m_j + 2mmax) nq + (n_i - n_j + 2nmax)
+            const zc v = LDS ? box[e] : cb[e];
+            out[((long)b * N + i) * N + j] = cx<T>((T)v.x, (T)v.y);
+        }
+    }
+}
+
+template <class T>
+int convmat_orders_t(int cplx, const void* grid, int batch, int n1, int n2, const int* mn, int N, int mmax, int nmax, void* out, void* ws,
+                     hipStream_t s) {
+    const int nq = 4 * nmax + 1, np = 4 * mmax + 1;
+    zc* T1 = reinterpret_cast<zc*>(ws);
+    zc* coef = T1 + (long)batch * n1 * nq;
+    const size_t sm1 = sizeof(zc) * 2 * (size_t)n2, sm2 = sizeof(zc) * 2 * (size_t)n1;
+    if (cplx) TRX_LAUNCH((dft_rows_kernel<T, true>), dim3(n1, batch), dim3(128), sm1, s, (const T*)grid, n1, n2, nmax, T1);
+    else      TRX_LAUNCH((dft_rows_kernel<T, false>), dim3(n1, batch), dim3(128), sm1, s, (const T*)grid, n1, n2, nmax, T1);
+    TRX_LAUNCH(dft_cols_kernel, dim3(nq, batch), dim3(128), sm2, s, (const zc*)T1, n1, n2, mmax, nmax, coef);
+    const size_t box = sizeof(zc) * (size_t)np * nq;
+    const dim3 g(cdiv_i(N, ORD_ROWS), batch), blk(N >= 256 ? 256 : (N > 64 ? 128 : 64));
+    if (box <= ORD_LDS_MAX) {
+        if (set_max_dyn_smem((const void*)orders_gather_kernel<T, true>, box)) return TRX_ERR_LAUNCH;
+        TRX_LAUNCH((orders_gather_kernel<T, true>), g, blk, box, s, (const zc*)coef, mn, N, mmax, nmax, (cx<T>*)out);
+    } else {
+        TRX_LAUNCH((orders_gather_kernel<T, false>), g, blk, 0, s, (const zc*)coef, mn, N, mmax, nmax, (cx<T>*)out);
+    }
+    TRX_CHECK_LAUNCH();
+    return TRX_OK;
+}
 }  // namespace
+
+int orders_check(hipStream_t s, const int* mn, int N, int mmax, int nmax) {
+    std::vector<int> h((size_t)2 * N);
+    if (hipMemcpyAsync(h.data(), mn, sizeof(int) * h.size(), hipMemcpyDeviceToHost, s) != hipSuccess) return TRX_ERR_LAUNCH;
+    if (hipStreamSynchronize(s) != hipSuccess) return TRX_ERR_LAUNCH;
+    for (int i = 0; i < N; ++i)
+        if (h[2 * i] < -mmax || h[2 * i] > mmax || h[2 * i + 1] < -nmax || h[2 * i + 1] > nmax) return TRX_ERR_ARG;
+    return TRX_OK;
+}
+
+int convmat_orders_checked(hipStream_t s, int dtype, int cplx, const void* grid, int batch, int n1, int n2, const int* mn, int N, int mmax,
+                           int nmax, void* out, void* ws) {
+    if (dtype == TRX_C64) return convmat_orders_t<float>(cplx, grid, batch, n1, n2, mn, N, mmax, nmax, out, ws, s);
+    return convmat_orders_t<double>(cplx, grid, batch, n1, n2, mn, N, mmax, nmax, out, ws, s);
+}
 }  // namespace trx
 
 extern "C" size_t trx_convmat_ws_bytes(int dtype, int batch, int nx, int ny, int ox, int oy) {
@@ -117,4 +188,23 @@ extern "C" int trx_convmat(int dtype, int grid_is_complex, const void* grid, int
     if (dtype == TRX_C64) return trx::convmat_t<float>(grid_is_complex, grid, batch, nx, ny, ox, oy, out, ws, s);
     if (dtype == TRX_C128) return trx::convmat_t<double>(grid_is_complex, grid, batch, nx, ny, ox, oy, out, ws, s);
     return TRX_ERR_DTYPE;
+}
+
+extern "C" size_t trx_convmat_orders_ws_bytes(int dtype, int batch, int n1, int n2, int N, int mmax, int nmax) {
+    (void)N;
+    return trx_convmat_ws_bytes(dtype, batch, n1, n2, mmax, nmax);
+}
+
+extern "C" int trx_convmat_orders(int dtype, int grid_is_complex, const void* grid, int batch, int n1, int n2, const int* mn, int N, int mmax,
+                                  int nmax, void* out, void* ws, size_t ws_bytes, void* stream) {
+    if (!grid || !mn || !out || !ws) return TRX_ERR_ARG;
+    if (batch <= 0 || N <= 0 || mmax < 0 || nmax < 0 || n1 <= 2 * mmax || n2 <= 2 * nmax) return TRX_ERR_ARG;
+    if (dtype != TRX_C64 && dtype != TRX_C128) return TRX_ERR_DTYPE;
+    if (ws_bytes < trx_convmat_orders_ws_bytes(dtype, batch, n1, n2, N, mmax, nmax)) return TRX_ERR_WORKSPACE;
+    if ((size_t)16 * 2 * (size_t)(n1 > n2 ? n1 : n2) > 64 * 1024) return TRX_ERR_UNSUPPORTED;
+    hipStream_t s = trx::api_stream(stream);
+    // every index must lie in the coefficient box: the list is small (N pairs), so it is checked on the host (one stream sync)
+    const int rc = trx::orders_check(s, mn, N, mmax, nmax);
+    if (rc) return rc;
+    return trx::convmat_orders_checked(s, dtype, grid_is_complex, grid, batch, n1, n2, mn, N, mmax, nmax, out, ws);
 }

@@ -69,8 +69,11 @@ __global__ __launch_bounds__(256) void nv_convert_kernel(const T* __restrict__ g
 }
 
 // Structure tensor of grid row x, blurred along y:  Jy[b, c, x, y] = sum_k w[k] J_c[x, y+k]   (c = xx, xy, yy)
+// SKEW (trx_normal_field_lattice): the physical gradient is h^-1 (du, dv) of the index-space central differences, h^-1 = [[rhx, hi01],
+// [hi10, rhy]]; otherwise (rhx du, rhy dv) with the rectangular spacings, exactly as trx_normal_field has always computed it.
+template <bool SKEW>
 __global__ __launch_bounds__(256) void nv_tensor_y_kernel(const zc* __restrict__ g, int nx, int ny, double sigma, int R, double rhx, double rhy,
-                                                          double* __restrict__ Jy) {
+                                                          double hi01, double hi10, double* __restrict__ Jy) {
     TRX_DYN_SMEM(smem);
     double* J = reinterpret_cast<double*>(smem);   // [3][ny]
     double* w = J + 3 * ny;                        // [2R+1]
@@ -80,8 +83,15 @@ __global__ __launch_bounds__(256) void nv_tensor_y_kernel(const zc* __restrict__
     const zc* rm = gb + (long)wrap(x - 1, nx) * ny;
     const zc* rp = gb + (long)wrap(x + 1, nx) * ny;
     for (int y = threadIdx.x; y < ny; y += blockDim.x) {
-        const zc gx = (0.5 * rhx) * (rp[y] - rm[y]);
-        const zc gy = (0.5 * rhy) * (r0[wrap(y + 1, ny)] - r0[wrap(y - 1, ny)]);
+        zc gx, gy;
+        if (SKEW) {
+            const zc du = 0.5 * (rp[y] - rm[y]), dv = 0.5 * (r0[wrap(y + 1, ny)] - r0[wrap(y - 1, ny)]);
+            gx = rhx * du + hi01 * dv;
+            gy = hi10 * du + rhy * dv;
+        } else {
+            gx = (0.5 * rhx) * (rp[y] - rm[y]);
+            gy = (0.5 * rhy) * (r0[wrap(y + 1, ny)] - r0[wrap(y - 1, ny)]);
+        }
         J[y] = norm2(gx);
         J[ny + y] = gx.x * gy.x + gx.y * gy.y;     // Re(gx conj(gy))
         J[2 * ny + y] = norm2(gy);
@@ -161,11 +171,18 @@ static inline size_t al256(size_t b) { return (b + 255) & ~(size_t)255; }
 // workspace of the field from a complex128 grid: the y-blurred tensor [B, 3, nx, ny] fp64
 static inline size_t field_core_bytes(int batch, int nx, int ny) { return al256(sizeof(double) * 3 * (size_t)batch * nx * ny); }
 
-int field_core(hipStream_t s, const zc* gz, int batch, int nx, int ny, double sigma, double hx, double hy, double* nn, double* Jy) {
+// hinv: NULL = the rectangular spacings hx, hy; else the row-major inverse of the cell matrix h (rows a1/nx, a2/ny) of a lattice
+int field_core(hipStream_t s, const zc* gz, int batch, int nx, int ny, double sigma, double hx, double hy, double* nn, double* Jy,
+               const double* hinv = nullptr) {
     const int R = nv_radius(sigma);
     const size_t lds1 = sizeof(double) * (3 * (size_t)ny + 2 * R + 1), lds2 = sizeof(double) * (2 * (size_t)R + 1);
-    if (set_max_dyn_smem((const void*)nv_tensor_y_kernel, lds1)) return TRX_ERR_LAUNCH;
-    TRX_LAUNCH(nv_tensor_y_kernel, dim3(nx, batch), dim3(256), lds1, s, gz, nx, ny, sigma, R, 1.0 / hx, 1.0 / hy, Jy);
+    if (hinv) {
+        if (set_max_dyn_smem((const void*)nv_tensor_y_kernel<true>, lds1)) return TRX_ERR_LAUNCH;
+        TRX_LAUNCH(nv_tensor_y_kernel<true>, dim3(nx, batch), dim3(256), lds1, s, gz, nx, ny, sigma, R, hinv[0], hinv[3], hinv[1], hinv[2], Jy);
+    } else {
+        if (set_max_dyn_smem((const void*)nv_tensor_y_kernel<false>, lds1)) return TRX_ERR_LAUNCH;
+        TRX_LAUNCH(nv_tensor_y_kernel<false>, dim3(nx, batch), dim3(256), lds1, s, gz, nx, ny, sigma, R, 1.0 / hx, 1.0 / hy, 0.0, 0.0, Jy);
+    }
     TRX_LAUNCH(nv_field_x_kernel, dim3(cdiv_i(ny, 64), cdiv_i(nx, 4), batch), dim3(256), lds2, s, (const double*)Jy, nx, ny, sigma, R, nn);
     TRX_CHECK_LAUNCH();
     return TRX_OK;
@@ -190,9 +207,10 @@ struct NvLayout {                   // byte offsets into the workspace of trx_co
     size_t cws_bytes, inv_bytes;
 };
 
-NvLayout nv_layout(int dtype, int batch, int nx, int ny, int ox, int oy) {
+// Nlist < 0: the rectangle of (ox, oy); else a list of Nlist harmonics within |m| <= ox, |n| <= oy (trx_convmat_nv_orders)
+NvLayout nv_layout(int dtype, int batch, int nx, int ny, int ox, int oy, int Nlist = -1) {
     NvLayout L;
-    const size_t per = (size_t)nx * ny, N = (size_t)(2 * ox + 1) * (2 * oy + 1), NN = N * N, B = (size_t)batch;
+    const size_t per = (size_t)nx * ny, N = Nlist < 0 ? (size_t)(2 * ox + 1) * (2 * oy + 1) : (size_t)Nlist, NN = N * N, B = (size_t)batch;
     size_t o = 0;
     L.gz = o;  o += al256(sizeof(zc) * B * per);
     L.rz = o;  o += al256(sizeof(zc) * B * per);
@@ -211,12 +229,20 @@ NvLayout nv_layout(int dtype, int batch, int nx, int ny, int ox, int oy) {
     return L;
 }
 
+// mn == NULL: the rectangle of (ox, oy) (trx_convmat); else the device list mn[Nlist] with mmax = ox, nmax = oy (trx_convmat_orders).
+// hinv: NULL = spacings hx, hy; else the inverse cell matrix of a lattice (field_core).
 template <class T>
 int convmat_nv_t(int cplx, const void* grid, int batch, int nx, int ny, int ox, int oy, double sigma, double hx, double hy, const double* nn_in,
-                 void* Exx, void* Exy, void* Eyy, int* info, char* ws, int dtype, hipStream_t s) {
-    const NvLayout L = nv_layout(dtype, batch, nx, ny, ox, oy);
+                 void* Exx, void* Exy, void* Eyy, int* info, char* ws, int dtype, hipStream_t s, const int* mn = nullptr, int Nlist = -1,
+                 const double* hinv = nullptr) {
+    const NvLayout L = nv_layout(dtype, batch, nx, ny, ox, oy, mn ? Nlist : -1);
     const long per = (long)nx * ny;
-    const int N = (2 * ox + 1) * (2 * oy + 1);
+    const int N = mn ? Nlist : (2 * ox + 1) * (2 * oy + 1);
+    // the list was checked once by trx_convmat_nv_orders: the three gathers below do not check (and synchronise) again
+    auto conv = [&](int gc, const void* g, int nb, void* out) {
+        return mn ? convmat_orders_checked(s, TRX_C128, gc, g, nb, nx, ny, mn, N, ox, oy, out, ws + L.cws)
+                  : trx_convmat(TRX_C128, gc, g, nb, nx, ny, ox, oy, out, ws + L.cws, L.cws_bytes, s);
+    };
     const long NN = (long)N * N, bNN = (long)batch * NN;
     zc* gz = (zc*)(ws + L.gz);
     zc* rz = (zc*)(ws + L.rz);
@@ -236,15 +262,14 @@ int convmat_nv_t(int cplx, const void* grid, int batch, int nx, int ny, int ox, 
     const double* nn = nn_in;
     if (!nn) {
         double* nw = (double*)(ws + L.nn);
-        rc = field_core(s, gz, batch, nx, ny, sigma, hx, hy, nw, (double*)(ws + L.jy));
+        rc = field_core(s, gz, batch, nx, ny, sigma, hx, hy, nw, (double*)(ws + L.jy), hinv);
         if (rc) return rc;
         nn = nw;
     }
-    void* cws = ws + L.cws;
     // [eps] -> Exx (copied to Eyy below), [1/eps] -> R, [N_c] -> C[b*3 + c]
-    if ((rc = trx_convmat(TRX_C128, 1, gz, batch, nx, ny, ox, oy, oxx, cws, L.cws_bytes, s))) return rc;
-    if ((rc = trx_convmat(TRX_C128, 1, rz, batch, nx, ny, ox, oy, R, cws, L.cws_bytes, s))) return rc;
-    if ((rc = trx_convmat(TRX_C128, 0, nn, 3 * batch, nx, ny, ox, oy, C, cws, L.cws_bytes, s))) return rc;
+    if ((rc = conv(1, gz, batch, oxx))) return rc;
+    if ((rc = conv(1, rz, batch, R))) return rc;
+    if ((rc = conv(0, nn, 3 * batch, C))) return rc;
     if (hipMemcpyAsync(oyy, oxx, sizeof(zc) * (size_t)bNN, hipMemcpyDeviceToDevice, s) != hipSuccess) return TRX_ERR_LAUNCH;
     if ((rc = trx_inverse(TRX_C128, R, N, batch, piv, iinfo, ws + L.inv, L.inv_bytes, s))) return rc;
     TRX_LAUNCH(nv_info_kernel, dim3(cdiv_i(batch, 256)), dim3(256), 0, s, (const int*)iinfo, batch, info);
@@ -391,6 +416,65 @@ extern "C" int trx_convmat_nv(int dtype, int grid_is_complex, const void* grid, 
     if (dtype == TRX_C64)
         return convmat_nv_t<float>(grid_is_complex, grid, batch, nx, ny, ox, oy, sigma, hx, hy, nn, Exx, Exy, Eyy, info, (char*)ws, dtype, s);
     return convmat_nv_t<double>(grid_is_complex, grid, batch, nx, ny, ox, oy, sigma, hx, hy, nn, Exx, Exy, Eyy, info, (char*)ws, dtype, s);
+}
+
+// inverse of the cell matrix h (row-major, rows a1/n1 and a2/n2); false if h is not finite or (nearly) singular
+static bool cell_inverse(const double* h, double* hinv) {
+    if (!h) return false;
+    for (int k = 0; k < 4; ++k)
+        if (!std::isfinite(h[k])) return false;
+    const double det = h[0] * h[3] - h[1] * h[2];
+    if (!(std::fabs(det) > 1e-9 * std::hypot(h[0], h[1]) * std::hypot(h[2], h[3]))) return false;
+    hinv[0] = h[3] / det; hinv[1] = -h[1] / det; hinv[2] = -h[2] / det; hinv[3] = h[0] / det;
+    return true;
+}
+
+static inline bool cell_is_rect(const double* h) { return h[1] == 0.0 && h[2] == 0.0 && h[0] > 0.0 && h[3] > 0.0; }
+
+extern "C" int trx_normal_field_lattice(int dtype, int grid_is_complex, const void* grid, int batch, int n1, int n2, double sigma, const double* h,
+                                        double* nn, void* ws, size_t ws_bytes, void* stream) {
+    double hinv[4];
+    if (!grid || !nn || !ws || !cell_inverse(h, hinv) || !field_args_ok(batch, n1, n2, sigma, 1.0, 1.0)) return TRX_ERR_ARG;
+    if (cell_is_rect(h)) return trx_normal_field(dtype, grid_is_complex, grid, batch, n1, n2, sigma, h[0], h[3], nn, ws, ws_bytes, stream);
+    if (dtype != TRX_C64 && dtype != TRX_C128) return TRX_ERR_DTYPE;
+    if (ws_bytes < trx_normal_field_ws_bytes(dtype, batch, n1, n2)) return TRX_ERR_WORKSPACE;
+    if (n1 > 2048 || n2 > 2048 || sigma > NV_SIGMA_MAX) return TRX_ERR_UNSUPPORTED;
+    hipStream_t s = trx::api_stream(stream);
+    zc* gz = (zc*)ws;
+    double* Jy = (double*)((char*)ws + al256(sizeof(zc) * (size_t)batch * n1 * n2));
+    const long per = (long)n1 * n2;
+    int rc = dtype == TRX_C64 ? convert<float>(s, grid_is_complex, grid, batch, per, gz, nullptr, nullptr)
+                              : convert<double>(s, grid_is_complex, grid, batch, per, gz, nullptr, nullptr);
+    if (rc) return rc;
+    return field_core(s, gz, batch, n1, n2, sigma, 1.0, 1.0, nn, Jy, hinv);
+}
+
+extern "C" size_t trx_convmat_nv_orders_ws_bytes(int dtype, int batch, int n1, int n2, int N, int mmax, int nmax) {
+    if (batch <= 0 || N <= 0 || mmax < 0 || nmax < 0 || n1 <= 0 || n2 <= 0) return 0;
+    return nv_layout(dtype, batch, n1, n2, mmax, nmax, N).total;
+}
+
+extern "C" int trx_convmat_nv_orders(int dtype, int grid_is_complex, const void* grid, int batch, int n1, int n2, const int* mn, int N, int mmax,
+                                     int nmax, double sigma, const double* h, const double* nn, void* Exx, void* Exy, void* Eyy, int* info,
+                                     void* ws, size_t ws_bytes, void* stream) {
+    double hinv[4] = {1.0, 0.0, 0.0, 1.0};
+    if (!grid || !mn || !Exx || !Exy || !Eyy || !info || !ws) return TRX_ERR_ARG;
+    if (batch <= 0 || N <= 0 || mmax < 0 || nmax < 0 || n1 <= 2 * mmax || n2 <= 2 * nmax) return TRX_ERR_ARG;
+    if (!nn && (!cell_inverse(h, hinv) || !field_args_ok(batch, n1, n2, sigma, 1.0, 1.0))) return TRX_ERR_ARG;
+    if (dtype != TRX_C64 && dtype != TRX_C128) return TRX_ERR_DTYPE;
+    if (ws_bytes < trx_convmat_nv_orders_ws_bytes(dtype, batch, n1, n2, N, mmax, nmax)) return TRX_ERR_WORKSPACE;
+    if (n1 > 2048 || n2 > 2048 || (!nn && sigma > NV_SIGMA_MAX)) return TRX_ERR_UNSUPPORTED;
+    if ((size_t)16 * 2 * (size_t)(n1 > n2 ? n1 : n2) > 64 * 1024) return TRX_ERR_UNSUPPORTED;   // the DFT rows of trx_convmat_orders
+    hipStream_t s = trx::api_stream(stream);
+    if (int rc = orders_check(s, mn, N, mmax, nmax)) return rc;
+    // a rectangular cell takes the spacings path of trx_normal_field (same field bit for bit)
+    const bool rect = nn || cell_is_rect(h);
+    const double hx = rect && h ? h[0] : 1.0, hy = rect && h ? h[3] : 1.0;
+    if (dtype == TRX_C64)
+        return convmat_nv_t<float>(grid_is_complex, grid, batch, n1, n2, mmax, nmax, sigma, hx, hy, nn, Exx, Exy, Eyy, info, (char*)ws, dtype, s,
+                                   mn, N, rect ? nullptr : hinv);
+    return convmat_nv_t<double>(grid_is_complex, grid, batch, n1, n2, mmax, nmax, sigma, hx, hy, nn, Exx, Exy, Eyy, info, (char*)ws, dtype, s,
+                                mn, N, rect ? nullptr : hinv);
 }
 
 extern "C" int trx_build_pq_tensor(int dtype, const void* Exx, const void* Exy, const void* Eyy, const void* Einv, const void* Mu,

@@ -135,6 +135,28 @@ class Engine:
                                         ws.data_ptr(), nws, self.stream))
         return out
 
+    def _orders(self, mn, mmax=None, nmax=None):
+        """[N,2] harmonic list -> (contiguous int32 tensor on the device, N, mmax, nmax); the box defaults to the list's largest |m|, |n|."""
+        mn = torch.as_tensor(mn)
+        if mmax is None or nmax is None:
+            mmax, nmax = (int(v) for v in mn.detach().abs().amax(dim=0).cpu())
+        return self._c(mn.to(device=self.device, dtype=torch.int32)), int(mn.shape[0]), int(mmax), int(nmax)
+
+    @_phase("assembly (convolution matrices, E^-1, A = PQ)")
+    def convmat_orders(self, grid, mn, dtype, mmax=None, nmax=None):
+        """[B,n1,n2] real/complex grid and [N,2] harmonic list (m, n) -> [B,N,N] convolution matrix out[b,i,j] = c[m_i-m_j, n_i-n_j]
+        (include/trx.h: trx_convmat_orders).  mmax / nmax: the coefficient box (default: the largest |m| / |n| of the list)."""
+        B, n1, n2 = grid.shape
+        cplx = grid.is_complex()
+        grid = self._c(grid.to(dtype if cplx else _REAL[dtype]))
+        mn, N, mmax, nmax = self._orders(mn, mmax, nmax)
+        out = torch.empty((B, N, N), dtype=dtype, device=self.device)
+        nws = self.lib.convmat_orders_ws_bytes(_CODE[dtype], B, n1, n2, N, mmax, nmax)
+        ws = self._ws(nws)
+        self.lib.check(self.lib.convmat_orders(_CODE[dtype], int(cplx), grid.data_ptr(), B, n1, n2, mn.data_ptr(), N, mmax, nmax, out.data_ptr(),
+                                               ws.data_ptr(), nws, self.stream))
+        return out
+
     @_phase("assembly (convolution matrices, E^-1, A = PQ)")
     def convmat_li(self, grid, ox, oy, dtype, keep_inverses=False):
         """[B,nx,ny] grid -> (Ex, Ey) [B,N,N], Li's inverse-rule convolution matrices of the x and y field components (include/trx.h:
@@ -198,6 +220,52 @@ class Engine:
                                            nn.data_ptr() if nn is not None else None, Exx.data_ptr(), Exy.data_ptr(), Eyy.data_ptr(),
                                            info.data_ptr(), ws.data_ptr(), nws, self.stream))
         self._info(info, "convmat_nv (1: zero grid value, 2: singular [1/eps])")
+        return Exx, Exy, Eyy
+
+    @staticmethod
+    def _cell(h):
+        """host double[4] (row-major 2 x 2 cell matrix) for the C ABI."""
+        return (ctypes.c_double * 4)(*torch.as_tensor(h, dtype=torch.float64).reshape(4).tolist())
+
+    @_phase("assembly (convolution matrices, E^-1, A = PQ)")
+    def normal_field_lattice(self, grid, sigma, h):
+        """normal_field on an oblique cell: h is the 2 x 2 cell matrix, rows a1/n1 and a2/n2 (include/trx.h: trx_normal_field_lattice)."""
+        B, n1, n2 = grid.shape
+        cplx = grid.is_complex()
+        dt = grid.dtype if grid.dtype in (torch.float32, torch.complex64) else (torch.complex128 if cplx else torch.float64)
+        grid = self._c(grid.to(dt))
+        code = _lib.C64 if dt in (torch.float32, torch.complex64) else _lib.C128
+        nn = torch.empty((B, 3, n1, n2), dtype=torch.float64, device=self.device)
+        nws = self.lib.normal_field_ws_bytes(code, B, n1, n2)
+        ws = self._ws(nws)
+        self.lib.check(self.lib.normal_field_lattice(code, int(cplx), grid.data_ptr(), B, n1, n2, float(sigma), self._cell(h), nn.data_ptr(),
+                                                     ws.data_ptr(), nws, self.stream))
+        return nn
+
+    @_phase("assembly (convolution matrices, E^-1, A = PQ)")
+    def convmat_nv_orders(self, grid, mn, dtype, *, sigma=None, h=None, nn=None, mmax=None, nmax=None):
+        """convmat_nv for an [N,2] harmonic list on an oblique cell (include/trx.h: trx_convmat_nv_orders): (Exx, Exy, Eyy) [B,N,N].
+        h: the 2 x 2 cell matrix (rows a1/n1, a2/n2) that orients the derived field; nn: [B,3,n1,n2] float64 products of a supplied field."""
+        B, n1, n2 = grid.shape
+        cplx = grid.is_complex()
+        grid = self._c(grid.to(dtype if cplx else _REAL[dtype]))
+        mn, N, mmax, nmax = self._orders(mn, mmax, nmax)
+        Exx = torch.empty((B, N, N), dtype=dtype, device=self.device)
+        Exy, Eyy = torch.empty_like(Exx), torch.empty_like(Exx)
+        if nn is not None:
+            nn = self._c(nn.to(device=self.device, dtype=torch.float64))
+            if tuple(nn.shape) != (B, 3, n1, n2):
+                raise ValueError(f"normal-field products must be [{B}, 3, {n1}, {n2}], got {list(nn.shape)}")
+        elif sigma is None or h is None:
+            raise ValueError("convmat_nv_orders needs sigma and h when no field is supplied")
+        info = self._ints(B)
+        nws = self.lib.convmat_nv_orders_ws_bytes(_CODE[dtype], B, n1, n2, N, mmax, nmax)
+        ws = self._ws(nws)
+        self.lib.check(self.lib.convmat_nv_orders(_CODE[dtype], int(cplx), grid.data_ptr(), B, n1, n2, mn.data_ptr(), N, mmax, nmax,
+                                                  float(sigma or 0.0), self._cell(h) if h is not None else None,
+                                                  nn.data_ptr() if nn is not None else None, Exx.data_ptr(), Exy.data_ptr(), Eyy.data_ptr(),
+                                                  info.data_ptr(), ws.data_ptr(), nws, self.stream))
+        self._info(info, "convmat_nv_orders (1: zero grid value, 2: singular [1/eps])")
         return Exx, Exy, Eyy
 
     # -- dense blocks ----------------------------------------------------------------------------------

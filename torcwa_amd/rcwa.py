@@ -79,8 +79,12 @@ class rcwa(FieldMixin):
     def return_layer(self, layer_num, nx=100, ny=100):                                  # rcwa.py:264-298
         """eps(x,y), mu(x,y) of a layer recovered from the truncated Fourier series held in its convolution matrix.
         Harmonic (i, j), |i| <= 2ox, |j| <= 2oy, is read from the first column / first row of the Toeplitz matrix and
-        placed at [i mod nx, j mod ny] (the reference's negative-index wrap); one gather + one inverse FFT per material."""
+        placed at [i mod nx, j mod ny] (the reference's negative-index wrap); one gather + one inverse FFT per material.
+        On the general path (oblique lattice / order list) the grid is in lattice coordinates (axis 0 along a1, axis 1 along a2) and is
+        rebuilt from the distinct differences (m_i - m_j, n_i - n_j) present in the order set."""
         import numpy as np
+        if self._b._general:
+            return self._return_layer_general(layer_num, nx, ny)
         ox, oy = self.order
         wy = 2 * oy + 1
         if 2 * ox >= nx or 2 * oy >= ny:
@@ -94,6 +98,26 @@ class rcwa(FieldMixin):
         keep = np.sort(len(flat) - 1 - first_rev)
         dev = self._device
         row_t, col_t, flat_t = (torch.as_tensor(a[keep], dtype=torch.int64, device=dev) for a in (row, col, flat))
+        outs = []
+        for conv in (self._b.eps_conv[layer_num][0], self._b.mu_conv[layer_num][0]):
+            f = torch.zeros(nx * ny, dtype=conv.dtype, device=dev)
+            f[flat_t] = conv[row_t, col_t]
+            outs.append((torch.fft.ifftn(f.reshape(nx, ny)) * nx * ny).to(self._dtype))
+        return outs[0], outs[1]
+
+    def _return_layer_general(self, layer_num, nx, ny):
+        import numpy as np
+        mn = self._b._mn
+        dm = mn[:, None, 0] - mn[None, :, 0]
+        dn = mn[:, None, 1] - mn[None, :, 1]
+        if 2 * self._b._mmax >= nx or 2 * self._b._nmax >= ny:
+            raise IndexError("index %d is out of bounds for a %d x %d grid" % (2 * max(self._b._mmax, self._b._nmax), nx, ny))
+        # one (i, j) per distinct difference: its first occurrence in row-major order
+        _, first = np.unique((dm * (4 * self._b._nmax + 1) + dn).ravel(), return_index=True)
+        row, col = first // len(mn), first % len(mn)
+        flat = (dm.ravel()[first] % nx) * ny + (dn.ravel()[first] % ny)
+        dev = self._device
+        row_t, col_t, flat_t = (torch.as_tensor(a, dtype=torch.int64, device=dev) for a in (row, col, flat))
         outs = []
         for conv in (self._b.eps_conv[layer_num][0], self._b.mu_conv[layer_num][0]):
             f = torch.zeros(nx * ny, dtype=conv.dtype, device=dev)
@@ -126,8 +150,10 @@ class rcwa(FieldMixin):
     order_y = property(lambda self: self._b.order_y)
     layer_N = property(lambda self: self._b.layer_N)
     thickness = property(lambda self: [t[0] for t in self._b.thickness])
-    Gx_norm = property(lambda self: self._b.Gx_norm[0].to(self._dtype))
-    Gy_norm = property(lambda self: self._b.Gy_norm[0].to(self._dtype))
+    Gx_norm = property(lambda self: self._u(self._b.Gx_norm))           # None on the general path (oblique lattice / order list)
+    Gy_norm = property(lambda self: self._u(self._b.Gy_norm))
+    G_norm = property(lambda self: self._u(self._b.G_norm))             # [2, 2]: rows b1 / f, b2 / f
+    orders = property(lambda self: self._b.orders)                      # [N, 2] (m, n) of every harmonic, in matrix order
     eps_in = property(lambda self: self._b.eps_in[0].to(self._dtype))
     mu_in = property(lambda self: self._b.mu_in[0].to(self._dtype))
     eps_out = property(lambda self: self._b.eps_out[0].to(self._dtype))

@@ -13,6 +13,7 @@ import numpy as np
 import torch
 
 from .batched import NV_SIGMA_DEFAULT, BatchedRCWA, check_fourier_rule
+from .lattice import parse_order
 
 _DATA = os.path.join(os.path.dirname(os.path.abspath(__file__)), "data")
 
@@ -110,7 +111,8 @@ def auto_chunk(B, order, n_layers, precision, device, dtype=torch.complex64, str
     one point fits -- instead of an allocator error in the middle of a solve."""
     if device.type != "cuda":
         return B
-    n = 2 * (2 * order[0] + 1) * (2 * order[1] + 1)
+    kind, box, mn = parse_order(order)          # [ox, oy] or an [N, 2] order list (oblique lattices, circular truncation): n = 2N
+    n = 2 * (2 * box[0] + 1) * (2 * box[1] + 1) if kind == "rect" else 2 * len(mn)
     # element size of the COMPUTE dtype: complex128 unless a complex64 problem is solved natively (BatchedRCWA: precision="native" only
     # halves the element of complex64 problems); `streams` chunks are resident at once when the sweep is dealt to several streams
     elem = 8 if (precision == "native" and dtype == torch.complex64) else 16
@@ -123,7 +125,7 @@ def auto_chunk(B, order, n_layers, precision, device, dtype=torch.complex64, str
     if fit < 1:
         raise RuntimeError("torcwa_amd sweep: one sweep point at order %s needs about %.1f GB of HBM (%d x %d complex matrices x %.0f), but only "
                            "%.1f GB are free on %s (%.1f GB total, %.0f %% kept as headroom); free memory or lower the order"
-                           % (list(order), per_point / 1e9, n, n, mats, free / 1e9, device, total / 1e9, 100 * _HEADROOM))
+                           % (list(box) if kind == "rect" else "of %d harmonics" % len(mn), per_point / 1e9, n, n, mats, free / 1e9, device, total / 1e9, 100 * _HEADROOM))
     if fit >= B:
         return B
     return fit if fit < 8 else fit - fit % 8
