@@ -284,6 +284,26 @@ size_t trx_build_a_tensor_ws_bytes(int dtype, int N, int batch);
 int trx_build_a_tensor(int dtype, const void* Exx, const void* Exy, const void* Eyy, const void* Einv, const void* mu, const void* kx, const void* ky,
                        int N, int batch, void* A, void* ws, size_t ws_bytes, void* stream);
 
+/* ---- power flux through the planes of a stack (no reference counterpart; the formulas are those of the reference's field maps,
+ *      torcwa/rcwa.py:708-755, reduced over the unit cell by Parseval) ------------------------------------------------------------------
+ * trx_matvec: Y[b] = A[b] X[b] for a skinny right-hand side.  A [batch,m,k]; X [batch,k,c] with element stride strideX between points
+ * (strideX = 0: one X shared by the batch); Y [batch,m,c]; 1 <= c <= 16, batch <= 65535.  One wave per row of A, fp64 accumulation for both
+ * dtypes, a fixed reduction tree (bitwise reproducible).  Used for [c+; c-] = C_layer E_i and for S_block E_i in the half-spaces.  No workspace. */
+int trx_matvec(int dtype, const void* A, const void* X, long strideX, void* Y, int m, int k, int c, int batch, void* stream);
+/* trx_layer_flux: the cell-averaged z component of Re(E x H*) at nz planes inside a layer, un-normalised,
+ *   flux[b,t] = Re sum_{j<N} ( e_j conj(h_{j+N}) - e_{j+N} conj(h_j) ),   e = W (a + b),  h = V (a - b)          (n = 2N rows: x then y)
+ *   a_k = cplus_k exp(i omega kz_k z),   b_k = cminus_k exp(i omega kz_k (d - z)),   z = z[b,t]  (z_is_fraction: z[b,t] d[b])
+ * W, V [batch,n,n] (E_eigvec, H_eigvec; 16-byte aligned), cplus, cminus, kz [batch,n] in `dtype` (element alignment suffices); omega, d [batch],
+ * z [batch,nz] and the output flux [batch,nz] are float64.  nz = 0 or batch = 0 returns TRX_OK without touching any buffer (ws may be NULL).  The phase factors are formed in the kernel; neither the [n,nz] right-hand sides nor the products W(a+b), V(a-b)
+ * are written to memory.  Traffic model: W and V are read once per tile of up to 16 planes (2 n^2 elements per point and tile; 118 MB at
+ * n = 1922 in complex128), everything else is O(n nz).  Dot products and the sum over j are accumulated in fp64 for both dtypes.  Deterministic:
+ * each workgroup (32 harmonics j, i.e. the four row blocks the sum pairs) writes one partial per plane to the workspace and a second kernel adds
+ * them in a fixed order; no floating-point atomics.  ws: trx_layer_flux_ws_bytes (ceil(N/32) nz batch doubles), 16-byte aligned. */
+size_t trx_layer_flux_ws_bytes(int dtype, int N, int nz, int batch);
+int trx_layer_flux(int dtype, const void* W, const void* V, const void* cplus, const void* cminus, const void* kz, const double* omega,
+                   const double* d, const double* z, int z_is_fraction, int N, int nz, int batch, double* flux, void* ws, size_t ws_bytes,
+                   void* stream);
+
 /* ---- measurement aid (no reference counterpart): HIP-event timing of the dominant kernels --------------------
  * trx_prof_enable(1) makes the instrumented launch sites record hipEvents on the launch stream.  Sampling is systematic and
  * uniform over the run: every stride-th launch of a tag is timed; when the pool (2048 event pairs per tag) is full every

@@ -15,6 +15,7 @@ import torch
 from .engine import Engine, default_engine
 from . import autograd_ops as ag
 from . import lattice as _lat
+from .flux import FluxMixin
 from .torch_eig import Eig
 
 # torcwa/rcwa.py:5 -- the reference's pi (typo in the 9th decimal) is part of its observable behaviour
@@ -79,7 +80,7 @@ def _halfspace_V(kx, ky, epsmu):
     return BlockDiag2(-ky * kx / kz, -kz - ky ** 2 / kz, kz + kx ** 2 / kz, kx * ky / kz)
 
 
-class BatchedRCWA:
+class BatchedRCWA(FluxMixin):
     def __init__(self, freq, order, L, *, batch=None, dtype=torch.complex64, device=None, stable_eig_grad=True,
                  avoid_Pinv_instability=False, max_Pinv_instability=0.005, precision="high", engine=None,
                  keep_coupling=True, fold_layers=False, eig_route="auto", route_hint=None, fourier_rule="laurent", nv_sigma=NV_SIGMA_DEFAULT):

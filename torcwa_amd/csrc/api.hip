@@ -3,7 +3,7 @@
 
 using namespace trx;
 
-extern "C" int trx_version(void) { return 400; }   // 0.4.0: trx_convmat_orders, trx_normal_field_lattice, trx_convmat_nv_orders
+extern "C" int trx_version(void) { return 500; }   // 0.5.0: trx_matvec, trx_layer_flux
 
 extern "C" const char* trx_strerror(int code) {
     switch (code) {

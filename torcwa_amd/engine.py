@@ -528,6 +528,42 @@ class Engine:
         self.lib.check(self.lib.build_a_tensor(_CODE[dt], *[t.data_ptr() for t in ops], N, B, A.data_ptr(), ws.data_ptr(), nws, self.stream))
         return A
 
+    # -- power flux ------------------------------------------------------------------------------------
+    @_phase("power flux (trx_matvec, trx_layer_flux)")
+    def matvec(self, A, X):
+        """Y[b] = A[b] X[b] for A [B,m,k] and a skinny X [B,k,c] or [k,c] (shared by the batch), 1 <= c <= 16 (include/trx.h: trx_matvec)."""
+        A, X = self._c(A), self._c(X)
+        self._check(A, X)
+        B, m, k = A.shape
+        shared = X.dim() == 2
+        c = X.shape[-1]
+        if X.shape[-2] != k or (not shared and X.shape[0] != B) or not (1 <= c <= 16):
+            raise ValueError(f"matvec: A {list(A.shape)} against X {list(X.shape)} (X is [B,k,c] or [k,c] with 1 <= c <= 16)")
+        Y = torch.empty((B, m, c), dtype=A.dtype, device=self.device)
+        self.lib.check(self.lib.matvec(_CODE[A.dtype], A.data_ptr(), X.data_ptr(), 0 if shared else k * c, Y.data_ptr(), m, k, c, B, self.stream))
+        return Y
+
+    @_phase("power flux (trx_matvec, trx_layer_flux)")
+    def layer_flux(self, W, V, cplus, cminus, kz, omega, d, z, *, z_is_fraction=False):
+        """[B,nz] float64 un-normalised power flux through the planes z [B,nz] of a layer (include/trx.h: trx_layer_flux).  W, V [B,n,n];
+        cplus, cminus, kz [B,n]; omega, d [B] real."""
+        W, V, cplus, cminus, kz = (self._c(t) for t in (W, V, cplus, cminus, kz))
+        self._check(W, V, cplus, cminus, kz)
+        B, n, _ = W.shape
+        f64 = lambda t: self._c(t.to(device=self.device, dtype=torch.float64))
+        omega, d, z = f64(omega), f64(d), f64(z)
+        nz = z.shape[1]
+        if tuple(V.shape) != (B, n, n) or any(tuple(t.shape) != (B, n) for t in (cplus, cminus, kz)) or omega.shape != (B,) or d.shape != (B,) \
+                or z.shape[0] != B or n % 2:
+            raise ValueError("layer_flux: W, V [B,n,n]; cplus, cminus, kz [B,n]; omega, d [B]; z [B,nz]")
+        flux = torch.empty((B, nz), dtype=torch.float64, device=self.device)
+        nws = self.lib.layer_flux_ws_bytes(_CODE[W.dtype], n // 2, nz, B)
+        ws = self._ws(nws)
+        self.lib.check(self.lib.layer_flux(_CODE[W.dtype], W.data_ptr(), V.data_ptr(), cplus.data_ptr(), cminus.data_ptr(), kz.data_ptr(),
+                                           omega.data_ptr(), d.data_ptr(), z.data_ptr(), int(bool(z_is_fraction)), n // 2, nz, B, flux.data_ptr(),
+                                           ws.data_ptr(), nws, self.stream))
+        return flux
+
 
 _default = None
 

@@ -76,6 +76,29 @@ class rcwa(FieldMixin):
     def _matching_indices(self, orders):
         return self._b._matching_indices(orders)
 
+    # ---- power flux and absorption (extension): un-batched views of BatchedRCWA.power_flux / absorption -------
+    def _flux_source(self):
+        """Hand the source of source_planewave / source_fourier (fields.py) to the batched solver."""
+        if hasattr(self, "_E_i"):
+            self._b._E_i = self._E_i.reshape(1, -1)
+            self._b.source_direction = self.source_direction
+
+    def power_flux(self, layer_num, z_prop=0., *, normalize=True):
+        """Real [nz]: the power flux through the planes at in-layer offsets z_prop (scalar or [nz]) of layer `layer_num` (-1 .. layer_N as in
+        field_xy), for the source set by source_planewave / source_fourier; normalize=True divides by the incident flux (torcwa_amd/flux.py)."""
+        self._flux_source()
+        return self._b.power_flux(layer_num, z_prop, normalize=normalize)[0]
+
+    def incident_flux(self):
+        """Scalar: the flux of the source wave alone in its own half-space (negative for a backward source: counted along +z)."""
+        self._flux_source()
+        return self._b.incident_flux()[0]             # TrxError without a source, like power_flux and absorption
+
+    def absorption(self):
+        """{"layers": [layer_N], "R", "T", "A": scalars}: per-layer absorbed, reflected and transmitted fractions of the incident flux."""
+        self._flux_source()
+        return {k: v[0] for k, v in self._b.absorption().items()}
+
     def return_layer(self, layer_num, nx=100, ny=100):                                  # rcwa.py:264-298
         """eps(x,y), mu(x,y) of a layer recovered from the truncated Fourier series held in its convolution matrix.
         Harmonic (i, j), |i| <= 2ox, |j| <= 2oy, is read from the first column / first row of the Toeplitz matrix and

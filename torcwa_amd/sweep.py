@@ -78,9 +78,11 @@ def rectangle_density(nx, ny, Lx, Ly, Wx, Wy, Cx, Cy, theta=0.0, edge_sharpness=
 
 
 def _solve_chunk(freq, layers, order, L, eps_in, eps_out, inc_ang, azi_ang, dtype, precision, engine, orders,
-                 polarization, direction, port, check_info, eig_route="auto", route_hint=None, fourier_rule="laurent", nv_sigma=NV_SIGMA_DEFAULT):
-    """layers: list of (thickness, eps[, mu]); thickness scalar or [b]; eps/mu scalar, [b] or [b,nx,ny]."""
-    sim = BatchedRCWA(freq, order, L, dtype=dtype, precision=precision, engine=engine, keep_coupling=False, fold_layers=True,
+                 polarization, direction, port, check_info, eig_route="auto", route_hint=None, fourier_rule="laurent", nv_sigma=NV_SIGMA_DEFAULT,
+                 absorption=False, source=None):
+    """layers: list of (thickness, eps[, mu]); thickness scalar or [b]; eps/mu scalar, [b] or [b,nx,ny].  absorption: the chunk keeps W, V and
+    the coupling matrices (keep_coupling=True, no streaming cascade) and returns (S-parameters, BatchedRCWA.absorption())."""
+    sim = BatchedRCWA(freq, order, L, dtype=dtype, precision=precision, engine=engine, keep_coupling=bool(absorption), fold_layers=not absorption,
                       eig_route=eig_route, route_hint=route_hint, fourier_rule=fourier_rule, nv_sigma=nv_sigma)
     if eps_in is not None:
         sim.add_input_layer(eps=eps_in)
@@ -90,7 +92,16 @@ def _solve_chunk(freq, layers, order, L, eps_in, eps_out, inc_ang, azi_ang, dtyp
     for lay in layers:
         sim.add_layer(*lay)
     sim.solve_global_smatrix()
-    return sim.S_parameters([list(o) for o in orders], direction=direction, port=port, polarization=polarization)
+    sp = sim.S_parameters([list(o) for o in orders], direction=direction, port=port, polarization=polarization)
+    if not absorption:
+        return sp
+    src = dict(amplitude=[1.0, 0.0], notation="xy", direction=direction)
+    src.update(source or {})
+    if "orders" in src:
+        sim.source_fourier(**src)
+    else:
+        sim.source_planewave(**src)
+    return sp, sim.absorption()
 
 
 # HBM footprint of one sweep point, in units of one n x n complex128 matrix (n = 2 (2 ox + 1)(2 oy + 1)): measured on MI355X with the caching
@@ -105,7 +116,17 @@ _NV_EXTRA = 2.0
 _HEADROOM = 0.10                               # fraction of the device memory a sweep leaves free
 
 
-def auto_chunk(B, order, n_layers, precision, device, dtype=torch.complex64, streams=1, fourier_rule="laurent"):
+# absorption=True (keep_coupling=True, no streaming cascade), matrices per point and layer on top of _POINT_MATRICES.  Derived from the code: every
+# layer keeps W, V, c+, c- (4), its S11, S21 (2) and, with the lean paths off, P, Q, M, M^-1 (4) = 10; the C lists hold one [2n, n] block per layer
+# in each direction (4 per layer), and a star product writes the new lists while the old ones are alive (4 per layer already folded) next to its
+# X / Y factors (4, once): 22 for one layer.  Measured on MI355X (profiles/flux_timing.txt: single patterned layer, order [15,15], 120 points):
+# 188.1 GB allocated / 210.9 GB reserved = 26.5 / 29.7 matrices per point in all, against 10.0 / 14.2 for the plain sweep -- the derived count was
+# too high (not all of its terms are alive at once).  What must fit is what the allocator reserves: 29.7 - 15.0 (_POINT_MATRICES) = 14.7 -> 15.
+# Only the one-layer case is measured; the count is applied per layer because every term of the derivation grows with the number of layers.
+_ABS_EXTRA_PER_LAYER = 15.0
+
+
+def auto_chunk(B, order, n_layers, precision, device, dtype=torch.complex64, streams=1, fourier_rule="laurent", absorption=False):
     """Largest number of points solved in lock-step that fits the free HBM of `device` with _HEADROOM to spare (a multiple of 8 when it
     is cut: the mixed-precision eigensolver and its iteration groups want batches of at least 8).  Raises with the numbers when not even
     one point fits -- instead of an allocator error in the middle of a solve."""
@@ -117,6 +138,8 @@ def auto_chunk(B, order, n_layers, precision, device, dtype=torch.complex64, str
     # halves the element of complex64 problems); `streams` chunks are resident at once when the sweep is dealt to several streams
     elem = 8 if (precision == "native" and dtype == torch.complex64) else 16
     mats = _POINT_MATRICES[1 if n_layers <= 1 else 2] + {"li": _LI_EXTRA, "normal": _NV_EXTRA}.get(fourier_rule, 0.0)
+    if absorption:
+        mats += _ABS_EXTRA_PER_LAYER * max(1, int(n_layers))
     per_point = mats * n * n * elem * max(1, int(streams))
     free, total = torch.cuda.mem_get_info(device)
     free += torch.cuda.memory_reserved(device) - torch.cuda.memory_allocated(device)      # the caching allocator's idle blocks are ours to reuse
@@ -139,10 +162,24 @@ def _slice(v, lo, hi, B):
     return v
 
 
+def _source_amplitudes(source, B):
+    """(M, per_point) of a sweep's source keywords: M orders, and whether `amplitude` carries a leading B.  Anything else is refused here,
+    before any chunk is solved."""
+    if not source or "amplitude" not in source:
+        return 1, False
+    M = int(torch.as_tensor(source["orders"]).numel() // 2) if "orders" in source else 1
+    k = int(torch.as_tensor(source["amplitude"]).numel())
+    if k == 2 * M:
+        return M, False
+    if k == 2 * M * B:
+        return M, True
+    raise ValueError(f"source amplitude must hold [{M}, 2] values (shared by the sweep) or [{B}, {M}, 2] (one per sweep point), got {k} values")
+
+
 def solve_stack_sweep(freq, layers, order, L, *, eps_in=None, eps_out=None, inc_ang=0.0, azi_ang=0.0, dtype=torch.complex64,
                       precision="high", engine=None, chunk=None, streams=1, orders=((0, 0),), polarization="xx",
                       direction="forward", port="transmission", check_info=True, eig_route="auto", fourier_rule="laurent",
-                      nv_sigma=NV_SIGMA_DEFAULT):
+                      nv_sigma=NV_SIGMA_DEFAULT, absorption=False, source=None):
     """B sweep points of a multi-layer stack (BASELINE.json configs 2-4): the reference's per-point Python loop
     (example/Example1-1.ipynb, Example3.ipynb) as chunks of a batched solve.  `layers` as in `_solve_chunk`, with
     per-point quantities carrying a leading dimension B = len(freq).  Returns the requested S-parameter [B, len(orders)].
@@ -151,33 +188,48 @@ def solve_stack_sweep(freq, layers, order, L, *, eps_in=None, eps_out=None, inc_
     of this call use the all-fp64 route -- BatchedRCWA._eig_call), "mixed" or "fp64".
 
     fourier_rule: "laurent" (default), "li" (Li's inverse rule in every patterned layer, BatchedRCWA) or "normal" (the normal-vector method,
-    the field derived from each grid with a Gaussian of nv_sigma cells)."""
+    the field derived from each grid with a Gaussian of nv_sigma cells).
+
+    absorption=True: every chunk is solved with keep_coupling=True and without the streaming cascade (more HBM per point: auto_chunk), the source
+    is applied -- `source`: keywords of BatchedRCWA.source_planewave, or of source_fourier when it has "orders"; default a unit plane wave,
+    amplitude [1, 0], notation "xy", in the call's `direction`; an amplitude with a leading B is cut into the chunks like every other per-point
+    input -- and the call returns
+    (S-parameters, absorption dict) with the dict's tensors ("layers" [B, n_layers], "R", "T", "A" [B]) concatenated over the chunks.  With the
+    default absorption=False the code path, the return value and the memory model are unchanged."""
     from .engine import default_engine
     check_fourier_rule(fourier_rule)
     B = freq.shape[0]
     eng = engine if engine is not None else default_engine()
     old_check, eng.check_info = eng.check_info, check_info         # restored below: the engine may be shared with other solvers
     # chunk=None: as many points in lock-step as the free HBM holds (the reference's per-point loop cannot run out of memory; neither must this)
-    chunk = (auto_chunk(B, order, len(layers), precision, freq.device, dtype=dtype, streams=streams, fourier_rule=fourier_rule) if not chunk
+    chunk = (auto_chunk(B, order, len(layers), precision, freq.device, dtype=dtype, streams=streams, fourier_rule=fourier_rule,
+                        **({"absorption": True} if absorption else {})) if not chunk
              else int(chunk))
     if streams > 1 and chunk >= B:
         chunk = -(-B // streams)
     spans = [(lo, min(B, lo + chunk)) for lo in range(0, B, chunk)]
     outs = [None] * len(spans)
     route_hint = {}                     # shared by the chunks of this call only
+    n_src, src_per_point = _source_amplitudes(source, B) if absorption else (1, False)
 
     def run(i):
         lo, hi = spans[i]
         lays = [tuple(_slice(v, lo, hi, B) for v in lay) for lay in layers]
+        src = source
+        if src_per_point:
+            src = dict(source, amplitude=torch.as_tensor(source["amplitude"]).reshape(B, n_src, 2)[lo:hi])
         outs[i] = _solve_chunk(freq[lo:hi], lays, order, L, _slice(eps_in, lo, hi, B), _slice(eps_out, lo, hi, B), _slice(inc_ang, lo, hi, B),
                                _slice(azi_ang, lo, hi, B), dtype, precision, engine, orders, polarization, direction, port, check_info,
-                               eig_route=eig_route, route_hint=route_hint, fourier_rule=fourier_rule, nv_sigma=nv_sigma)
+                               eig_route=eig_route, route_hint=route_hint, fourier_rule=fourier_rule, nv_sigma=nv_sigma,
+                               **({"absorption": True, "source": src} if absorption else {}))
 
     dev = freq.device
     try:
         _run_spans(run, spans, streams, dev)
     finally:
         eng.check_info = old_check
+    if absorption:
+        return (torch.cat([o[0] for o in outs], dim=0), {k: torch.cat([o[1][k] for o in outs], dim=0) for k in outs[0][1]})
     return torch.cat(outs, dim=0)
 
 
