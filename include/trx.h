@@ -262,6 +262,21 @@ size_t trx_redheffer_halfspace_ws_bytes(int dtype, int N, int batch, int side, i
 int trx_redheffer_halfspace(int dtype, int side, const void* bd, const void* const* S, void* const* Sout, void* XY, int N, int batch,
                             int* piv, int* info, void* ws, size_t ws_bytes, void* stream);
 
+/* PROBED half-space star product: m columns of ONE block of the product instead of its four n x n blocks -- what a sweep reads (S_parameters
+ * takes a few rows of one or two columns of one block, rcwa.py:300-524).  side, bd, S as trx_redheffer_halfspace; block = 0..3 in the order
+ * [S11, S21, S12, S22]; cols: HOST array of m column indices in [0, 2N), shared by the batch, 1 <= m <= 16; out [batch,n,m] receives
+ * out[b, :, q] = (block of Sin * S or S * Sout)[b, :, cols[q]].  With Sm * Sn, K = I - Sm12 Sn21 and e_c the unit vector of column c:
+ *   v = Sm11 e_c (blocks 0, 1)  or  Sm12 (Sn22 e_c) (blocks 2, 3);   u = K^-1 v;
+ *   block 0: Sn11 u;  block 1: Sm21 e_c + Sm22 (Sn21 u);  block 2: Sn12 e_c + Sn11 u;  block 3: Sm22 (Sn22 e_c + Sn21 u).
+ * K is an O(n^2) row (side 0) or column (side 1) combination, so the call costs one LU of K (n^3/3 complex MACs), one m-column solve and at
+ * most one dense mat-vec: 0.33 n^3 instead of 4.33 n^3.  The inputs are not modified and out must not alias them.  piv: int[batch*n];
+ * info: int[batch], set by the LU of K exactly as in trx_redheffer_halfspace (non-zero: singular K, that point's columns are not finite).
+ * ws: trx_redheffer_halfspace_columns_ws_bytes = one [batch,n,n] matrix for K and three [batch,n,m] column blocks.  batch <= 65535;
+ * TRX_ERR_ARG for a block, a column index or m out of range. */
+size_t trx_redheffer_halfspace_columns_ws_bytes(int dtype, int N, int batch, int m);
+int trx_redheffer_halfspace_columns(int dtype, int side, const void* bd, const void* const* S, int block, const int* cols, int m, void* out,
+                                    int N, int batch, int* piv, int* info, void* ws, size_t ws_bytes, void* stream);
+
 /* A = P Q (rcwa.py:1236) for a layer with homogeneous mu[batch], from its block structure (two N^3 GEMMs instead of
  * one (2N)^3): A = [[mu E - Ky^2 - Kx Gx, KxKy - Kx Gy],[KxKy - Ky Gx, mu E - Kx^2 - Ky Gy]], G* = Einv (K* E). */
 size_t trx_build_a_ws_bytes(int dtype, int N, int batch);

@@ -63,6 +63,9 @@ _SIGS = {
     "trx_redheffer": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "trx_redheffer_halfspace_ws_bytes": (c_size_t, [c_int, c_int, c_int, c_int, c_int]),
     "trx_redheffer_halfspace": (c_int, [c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "trx_redheffer_halfspace_columns_ws_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
+    "trx_redheffer_halfspace_columns": (c_int, [c_int, c_int, c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_int, c_void_p, c_void_p,
+                                                c_void_p, c_size_t, c_void_p]),
     "trx_build_a_ws_bytes": (c_size_t, [c_int, c_int, c_int]),
     "trx_build_a": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_size_t, c_void_p]),
     "trx_matvec": (c_int, [c_int, c_void_p, c_void_p, c_long, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),

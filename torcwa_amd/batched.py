@@ -686,7 +686,10 @@ class BatchedRCWA(FluxMixin):
             return [[], []]
         return [[torch.cat((self.Cplus[i], self.Cminus[i]), dim=1)], [torch.cat((self.Cminus[i], self.Cplus[i]), dim=1)]]
 
-    def solve_global_smatrix(self):                                                     # rcwa.py:173-211
+    def _cascade(self, defer_last=False):
+        """The cascade of solve_global_smatrix (rcwa.py:173-211): returns (S, C, None).  defer_last: when the LAST star product is one with a
+        half-space on the plain path -- a dense running S, no coupling lists to propagate (keep_coupling=False), no differentiable layer -- it is
+        not formed: (S before it, C, side) comes back, side 0 for the pending Sin * S, 1 for S * Sout (solve_S_parameters probes it)."""
         n, B = self.n, self.B
         self._zero_layer_S = False
         first = 1                                                                       # first stored layer still to be folded in
@@ -703,14 +706,42 @@ class BatchedRCWA(FluxMixin):
             self._zero_layer_S = not (self.has_in or self.has_out)     # reference stores 1-D zeros (rcwa.py:187-188)
         for i in range(first, self.layer_N):
             S, C = self._star(S, self._layer_S(i), C, self._layer_C(i))
-        if self.has_in:                                                                 # rcwa.py:198-202
-            S, C = self._star(self._Sin, S, [[], []], C)
-        if self.has_out:                                                                # rcwa.py:204-208
-            S, C = self._star(S, self._Sout, C, [[], []])
+        sides = ([0] if self.has_in else []) + ([1] if self.has_out else [])           # rcwa.py:198-202, 204-208
+        for j, side in enumerate(sides):
+            if (defer_last and j == len(sides) - 1 and not self.keep_coupling and not getattr(self, "_diff", False)
+                    and not self._is_bd(S) and not C[0] and not C[1]):
+                return S, C, side
+            S, C = self._star(self._Sin, S, [[], []], C) if side == 0 else self._star(S, self._Sout, C, [[], []])
+        return S, C, None
+
+    def solve_global_smatrix(self):                                                     # rcwa.py:173-211
+        S, C, _ = self._cascade()
         if self._is_bd(S):                                                              # only homogeneous media: densify for the read-out
             S = [blk.dense().to(self._cdtype) for blk in S]
         self.S = S
         self.C = C
+
+    def solve_S_parameters(self, orders, *, direction="forward", port="transmission", polarization="xx", ref_order=[0, 0],
+                           power_norm=True, evanscent=1e-3):
+        """solve_global_smatrix() followed by S_parameters(...) -- same arguments, warnings, in-place order clamping and values -- without the
+        global S-matrix where the read-out does not need it.  When the last star product of the cascade is one with a half-space on the plain
+        path (keep_coupling=False, no differentiable layer, a dense S before it), only the one or two columns of the one block that the
+        read-out takes are computed (Engine.redheffer_halfspace_columns: one LU instead of the 4.33 n^3 product), and `self.S` / `self.C` are
+        NOT set (they keep whatever an earlier solve_global_smatrix left).  Every other case -- keep_coupling, a differentiable stack, no
+        half-space, only homogeneous layers -- runs solve_global_smatrix() and reads out of self.S as S_parameters does."""
+        orders, polarization, oi, ri, k = self._sparam_args(orders, direction, port, polarization, ref_order)
+        S, C, side = self._cascade(defer_last=True)
+        if side is None:
+            if self._is_bd(S):
+                S = [blk.dense().to(self._cdtype) for blk in S]
+            self.S, self.C = S, C
+            Sk = S[k]
+            return self._sparam_values(lambda c: Sk[:, :, c], k, oi, ri, polarization, power_norm, evanscent)
+        cols = self._sparam_columns(ri, polarization)
+        Sbd = self._Sin if side == 0 else self._Sout
+        bd = torch.stack([torch.stack(blk.d, dim=0) for blk in Sbd], dim=0).to(self._cdtype).contiguous()   # [4,4,B,N]
+        out = self.engine.redheffer_halfspace_columns(side, bd, S, k, cols)             # [B, n, len(cols)]
+        return self._sparam_values(lambda c: out[:, :, cols.index(c)], k, oi, ri, polarization, power_norm, evanscent)
 
     # ---- a11 ---------------------------------------------------------------------------------------------
     def _matching_indices(self, orders):                                                # rcwa.py:1115-1122
@@ -736,8 +767,9 @@ class BatchedRCWA(FluxMixin):
         kz = torch.where(ev, repl, torch.real(kzc))
         return torch.cat((kz, kz), dim=1)                                               # [B, n]
 
-    def S_parameters(self, orders, *, direction="forward", port="transmission", polarization="xx", ref_order=[0, 0],
-                     power_norm=True, evanscent=1e-3):                                  # rcwa.py:300-524
+    def _sparam_args(self, orders, direction, port, polarization, ref_order):
+        """Argument handling of S_parameters (rcwa.py:300-340): warnings and defaults for invalid names, the order -> index map (clamps `orders`
+        in place).  Returns (orders, polarization, oi, ri, k) with k the block of S the (direction, port) pair reads."""
         dev = self._device
         orders = torch.as_tensor(orders, dtype=torch.int64, device=dev).reshape([-1, 2])
         if direction in _DIRS:
@@ -756,9 +788,24 @@ class BatchedRCWA(FluxMixin):
         ref_order = torch.as_tensor(ref_order, dtype=torch.int64, device=dev).reshape([1, 2])
         oi = self._matching_indices(orders)
         ri = self._matching_indices(ref_order)
-        N = self.order_N
-        k = _SBLOCK[(direction, port)]
+        return orders, polarization, oi, ri, _SBLOCK[(direction, port)]
+
+    def _sparam_columns(self, ri, polarization):
+        """Columns of the S block that _sparam_values reads: one in the xy basis, r0 and r0 + N in the ps basis."""
+        r0 = int(ri[0])
+        if polarization in ("xx", "yx", "xy", "yy"):
+            return [r0 + (self.order_N if polarization[1] == "y" else 0)]
+        return [r0, r0 + self.order_N]
+
+    def S_parameters(self, orders, *, direction="forward", port="transmission", polarization="xx", ref_order=[0, 0],
+                     power_norm=True, evanscent=1e-3):                                  # rcwa.py:300-524
+        orders, polarization, oi, ri, k = self._sparam_args(orders, direction, port, polarization, ref_order)
         Sk = self.S[k]
+        return self._sparam_values(lambda c: Sk[:, :, c], k, oi, ri, polarization, power_norm, evanscent)
+
+    def _sparam_values(self, col, k, oi, ri, polarization, power_norm, evanscent):
+        """Read-out and normalisation of S_parameters from the columns of block k: col(c) -> [B, n], column c of S[k] (one of _sparam_columns)."""
+        N = self.order_N
         num_side, den_side = _KZ_SIDES[k]
 
         if polarization in ("xx", "yx", "xy", "yy"):
@@ -766,7 +813,7 @@ class BatchedRCWA(FluxMixin):
                 oi = oi + N
             if polarization[1] == "y":
                 ri = ri + N
-            val = Sk[:, oi, ri[0]]                                                       # [B, M]
+            val = col(int(ri[0]))[:, oi]                                                 # [B, M]
             if power_norm:
                 kzn, kzd = self._kz_real(num_side, evanscent), self._kz_real(den_side, evanscent)
                 kxr = torch.cat((torch.real(self.Kx_norm_dn),) * 2, dim=1)
@@ -797,8 +844,9 @@ class BatchedRCWA(FluxMixin):
         o_inc, o_azi, o_ev = angles(oi, ok2, osign)
         r_inc, r_azi, r_ev = angles(ri, rk2, rsign)
         r0 = int(ri[0])
-        xx, xy = Sk[:, oi, r0], Sk[:, oi, r0 + N]
-        yx, yy = Sk[:, oi + N, r0], Sk[:, oi + N, r0 + N]
+        c0, c1 = col(r0), col(r0 + N)
+        xx, xy = c0[:, oi], c1[:, oi]
+        yx, yy = c0[:, oi + N], c1[:, oi + N]
         zero = torch.zeros_like(xx)
         xx, xy, yx, yy = (torch.where(o_ev, zero, t) for t in (xx, xy, yx, yy))
         co, so, ci = torch.cos(o_azi), torch.sin(o_azi), torch.cos(o_inc)

@@ -466,6 +466,30 @@ class Engine:
         X, Y = XY[0], XY[1]
         return out, X[:, :, :n], X[:, :, n:], Y[:, :, :n], Y[:, :, n:]
 
+    @_phase("Redheffer star products")
+    def redheffer_halfspace_columns(self, side, bd, S, block, cols):
+        """Columns `cols` (1 to 16 indices in [0, n), shared by the batch) of block `block` (0..3 = S11, S21, S12, S22) of the star product with
+        a block-diagonal half-space S-matrix (side 0: Sin * S, side 1: S * Sout), as [B, n, len(cols)]: one LU of K and O(n^2) work instead
+        of the four n x n blocks of `redheffer_halfspace` (include/trx.h: trx_redheffer_halfspace_columns)."""
+        S = [self._c(t) for t in S]
+        self._check(*S)
+        B, n, _ = S[0].shape
+        N = n // 2
+        dt = S[0].dtype
+        bd = self._c(bd.to(dt))
+        cols = [int(c) for c in cols]
+        m = len(cols)
+        out = torch.empty((B, n, m), dtype=dt, device=self.device)
+        piv, info = self._ints(B * n), self._ints(B)
+        nws = self.lib.redheffer_halfspace_columns_ws_bytes(_CODE[dt], N, B, m)
+        ws = self._ws(nws)
+        ps = (ctypes.c_void_p * 4)(*[t.data_ptr() for t in S])
+        pc = (ctypes.c_int * max(m, 1))(*cols)
+        self.lib.check(self.lib.redheffer_halfspace_columns(_CODE[dt], int(side), bd.data_ptr(), ctypes.addressof(ps), int(block), ctypes.addressof(pc), m,
+                                                            out.data_ptr(), N, B, piv.data_ptr(), info.data_ptr(), ws.data_ptr(), nws, self.stream))
+        self._info(info, "redheffer_halfspace_columns")
+        return out
+
     @_phase("assembly (convolution matrices, E^-1, A = PQ)")
     def build_a(self, E, Einv, mu, kx, ky):
         """A = P Q for homogeneous mu [B] via the block structure (two N^3 GEMMs)."""

@@ -91,10 +91,11 @@ def _solve_chunk(freq, layers, order, L, eps_in, eps_out, inc_ang, azi_ang, dtyp
     sim.set_incident_angle(inc_ang, azi_ang)
     for lay in layers:
         sim.add_layer(*lay)
+    if not absorption:
+        # only the column(s) of the one S block the read-out takes: the last half-space star product is probed, not formed
+        return sim.solve_S_parameters([list(o) for o in orders], direction=direction, port=port, polarization=polarization)
     sim.solve_global_smatrix()
     sp = sim.S_parameters([list(o) for o in orders], direction=direction, port=port, polarization=polarization)
-    if not absorption:
-        return sp
     src = dict(amplitude=[1.0, 0.0], notation="xy", direction=direction)
     src.update(source or {})
     if "orders" in src:
