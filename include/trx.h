@@ -326,6 +326,30 @@ int trx_layer_flux(int dtype, const void* W, const void* V, const void* cplus, c
                    const double* d, const double* z, int z_is_fraction, int N, int nz, int batch, double* flux, void* ws, size_t ws_bytes,
                    void* stream);
 
+/* ---- volume integrals inside a layer (no reference counterpart; the closed form other RCWA codes offer as a layer volume integral) -------
+ * trx_modal_overlap: out[b,r] = sum_{k,l} M[b,k,l] T_kl(z0, z1), (z0, z1) = zr[b,r] (z_is_fraction: times d[b]), the z integral over [z0, z1] of
+ * sum_kl M_kl conj(a_k + s b_k)(a_l + s b_l) with the mode amplitudes of trx_layer_flux,
+ *   a_k(z) = cplus_k e_k(z),   b_k(z) = cminus_k e_k(d - z),   e_k(z) = exp(i omega kz_k z),   Im kz >= 0   (|e_k| <= 1 on [0, d]):
+ *   T_kl = conj(c+_k) c+_l G++_kl + s conj(c+_k) c-_l G+-_kl + s conj(c-_k) c+_l G-+_kl + conj(c-_k) c-_l G--_kl
+ *   G++ = int conj(e_k(z)) e_l(z) dz       G+- = int conj(e_k(z)) e_l(d - z) dz
+ *   G-+ = int conj(e_k(d - z)) e_l(z) dz   G-- = int conj(e_k(d - z)) e_l(d - z) dz
+ * With M = Phi^H Gamma Phi this is (1 / cell) int int int w |F|^2 for the field F = Phi (a + s b) and the weight w whose convolution matrix is
+ * Gamma: Phi = W, s = +1 for [ex; ey]; V, s = -1 for [hx; hy]; [eps]^-1 (Ky V_x - Kx V_y), s = -1 for ez; [mu]^-1 (Kx W_y - Ky W_x), s = +1 for hz.
+ * End-point rule: every integrand is g(z) = exp(alpha z + beta) with |g| <= 1 on [0, d], and int_{z0}^{z1} g = g(z_e) D phi(x), D = z1 - z0,
+ * phi(x) = (e^x - 1) / x, with z_e = z0, x = alpha D where Re alpha <= 0 and z_e = z1, x = -alpha D otherwise: Re x <= 0, so nothing overflows
+ * and no 0 * inf appears however evanescent the modes.  phi is evaluated by its series for |x| < 1/2 and phi(0) = 1 exactly (the diagonal terms
+ * of a lossless propagating mode).  Ranges need not be ordered: z1 < z0 gives the negated integral of (z1, z0), bit for bit.
+ * M [batch,n,n] (16-byte aligned), cplus, cminus, kz [batch,n] in `dtype`; omega, d [batch] and zr [batch,nr,2] float64; s = +1 or -1; any n >= 1;
+ * out [batch,nr] complex128 for both dtypes (16-byte aligned).  nr = 0 or batch = 0 returns TRX_OK without touching any buffer (ws may be NULL);
+ * batch <= 65535; TRX_ERR_ARG for another s or nr < 0.  Exponents, phi and the sums are fp64 for both dtypes.  Traffic model: M is read once per
+ * tile of up to 16 ranges (n^2 elements per point and tile; 59 MB at n = 1922 in complex128), the end-point factors are O(n nr) and stay in LDS
+ * and registers; neither the G matrices nor T are written to memory.  Deterministic: each workgroup (16 rows of M) writes one partial per range
+ * to the workspace and a second kernel adds them in a fixed order; no floating-point atomics.
+ * ws: trx_modal_overlap_ws_bytes = 16 ceil(n/16) nr batch bytes, 16-byte aligned. */
+size_t trx_modal_overlap_ws_bytes(int dtype, int n, int nr, int batch);
+int trx_modal_overlap(int dtype, const void* M, const void* cplus, const void* cminus, const void* kz, const double* omega, const double* d,
+                      const double* zr, int z_is_fraction, int s, int n, int nr, int batch, void* out, void* ws, size_t ws_bytes, void* stream);
+
 /* ---- measurement aid (no reference counterpart): HIP-event timing of the dominant kernels --------------------
  * trx_prof_enable(1) makes the instrumented launch sites record hipEvents on the launch stream.  Sampling is systematic and
  * uniform over the run: every stride-th launch of a tag is timed; when the pool (2048 event pairs per tag) is full every

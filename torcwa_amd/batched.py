@@ -17,6 +17,7 @@ from . import autograd_ops as ag
 from . import lattice as _lat
 from .flux import FluxMixin
 from .torch_eig import Eig
+from .volume import VolumeMixin
 
 # torcwa/rcwa.py:5 -- the reference's pi (typo in the 9th decimal) is part of its observable behaviour
 PI_REF = 3.141592652589793
@@ -80,7 +81,7 @@ def _halfspace_V(kx, ky, epsmu):
     return BlockDiag2(-ky * kx / kz, -kz - ky ** 2 / kz, kz + kx ** 2 / kz, kx * ky / kz)
 
 
-class BatchedRCWA(FluxMixin):
+class BatchedRCWA(FluxMixin, VolumeMixin):
     def __init__(self, freq, order, L, *, batch=None, dtype=torch.complex64, device=None, stable_eig_grad=True,
                  avoid_Pinv_instability=False, max_Pinv_instability=0.005, precision="high", engine=None,
                  keep_coupling=True, fold_layers=False, eig_route="auto", route_hint=None, fourier_rule="laurent", nv_sigma=NV_SIGMA_DEFAULT):
@@ -172,6 +173,8 @@ class BatchedRCWA(FluxMixin):
         self.layer_N = 0
         self.thickness = []
         self.eps_conv, self.mu_conv = [], []
+        # keep_coupling: the eps / mu handed to add_layer, by reference (a grid) or as the per-point scalar [B] (absorption_by_region)
+        self.eps_grid, self.mu_grid = [], []
         self.eps_conv_x, self.eps_conv_y = [], []      # fourier_rule="li" with keep_coupling: Ex, Ey per layer (None: homogeneous / folded)
         # fourier_rule="normal" with keep_coupling: Exx, Exy (= Eyx), Eyy per layer (None: homogeneous eps / folded)
         self.eps_conv_xx, self.eps_conv_xy, self.eps_conv_yy = [], [], []
@@ -332,6 +335,8 @@ class BatchedRCWA(FluxMixin):
             Ex, Exy, Ey = conv_nv(eps)
         self.eps_conv.append(E)
         self.mu_conv.append(M)
+        self.eps_grid.append((self._bvec(eps) if eps_h else eps) if self.keep_coupling else None)
+        self.mu_grid.append((self._bvec(mu) if mu_h else mu) if self.keep_coupling else None)
         keep_li = li and self.keep_coupling and not eps_h
         self.eps_conv_x.append(Ex if keep_li else None)
         self.eps_conv_y.append(Ey if keep_li else None)
@@ -438,7 +443,7 @@ class BatchedRCWA(FluxMixin):
         self.layer_N += 1
         self.thickness.append(d)
         self.kz_norm.append(torch.cat((kz, kz), dim=1))
-        for lst in (self.eps_conv, self.mu_conv, self.eps_conv_x, self.eps_conv_y, self.eps_conv_xx, self.eps_conv_xy, self.eps_conv_yy,
+        for lst in (self.eps_conv, self.mu_conv, self.eps_grid, self.mu_grid, self.eps_conv_x, self.eps_conv_y, self.eps_conv_xx, self.eps_conv_xy, self.eps_conv_yy,
                     self.P, self.Q, self.E_eigvec, self.H_eigvec, self.Cplus, self.Cminus):
             lst.append(None)
 

@@ -3,7 +3,7 @@
 
 using namespace trx;
 
-extern "C" int trx_version(void) { return 600; }   // 0.6.0: trx_redheffer_halfspace_columns
+extern "C" int trx_version(void) { return 601; }   // 0.6.1: trx_modal_overlap
 
 extern "C" const char* trx_strerror(int code) {
     switch (code) {

@@ -588,6 +588,30 @@ class Engine:
                                            ws.data_ptr(), nws, self.stream))
         return flux
 
+    # -- volume integrals ------------------------------------------------------------------------------
+    @_phase("volume integrals (trx_modal_overlap)")
+    def modal_overlap(self, M, cplus, cminus, kz, omega, d, zr, s, z_is_fraction=False):
+        """[B,nr] complex128 sum_kl M_kl T_kl(z0, z1) over the ranges zr [B,nr,2] of a layer (include/trx.h: trx_modal_overlap).  M [B,n,n];
+        cplus, cminus, kz [B,n]; omega, d [B] real; s = +1 / -1."""
+        M, cplus, cminus, kz = (self._c(t) for t in (M, cplus, cminus, kz))
+        self._check(M, cplus, cminus, kz)
+        B, n, _ = M.shape
+        f64 = lambda t: self._c(t.to(device=self.device, dtype=torch.float64))
+        omega, d, zr = f64(omega), f64(d), f64(zr)
+        if M.shape[2] != n or any(tuple(t.shape) != (B, n) for t in (cplus, cminus, kz)) or omega.shape != (B,) or d.shape != (B,) \
+                or zr.dim() != 3 or zr.shape[0] != B or zr.shape[2] != 2:
+            raise ValueError("modal_overlap: M [B,n,n]; cplus, cminus, kz [B,n]; omega, d [B]; zr [B,nr,2]")
+        if int(s) not in (-1, 1):
+            raise ValueError(f"modal_overlap: s must be +1 or -1, got {s!r}")
+        nr = zr.shape[1]
+        out = torch.empty((B, nr), dtype=torch.complex128, device=self.device)
+        nws = self.lib.modal_overlap_ws_bytes(_CODE[M.dtype], n, nr, B)
+        ws = self._ws(nws)
+        self.lib.check(self.lib.modal_overlap(_CODE[M.dtype], M.data_ptr(), cplus.data_ptr(), cminus.data_ptr(), kz.data_ptr(), omega.data_ptr(),
+                                              d.data_ptr(), zr.data_ptr(), int(bool(z_is_fraction)), int(s), n, nr, B, out.data_ptr(), ws.data_ptr(),
+                                              nws, self.stream))
+        return out
+
 
 _default = None
 

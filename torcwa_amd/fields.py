@@ -227,7 +227,7 @@ class FieldMixin:
             z_prop = z_prop if z_prop <= 0. else 0.
         elif layer_num == b.layer_N:
             z_prop = z_prop if z_prop >= 0. else 0.
-        coeffs = self._coeffs(layer_num, torch.as_tensor([float(z_prop)], device=self._device))
+        coeffs = self._coeffs(layer_num, torch.as_tensor([float(z_prop)], dtype=torch.float64, device=self._device))     # not the fp32 default
         Px = torch.exp(1j * om * kx[None, :] * x).to(cdt)                                         # [nx, N]
         Py = torch.exp(1j * om * ky[:, None] * y).to(cdt)                                         # [N, ny]
         out = [self._mm(Px * c.reshape(1, -1).to(cdt), Py).to(self._dtype) for c in coeffs]

@@ -99,6 +99,19 @@ class rcwa(FieldMixin):
         self._flux_source()
         return {k: v[0] for k, v in self._b.absorption().items()}
 
+    # ---- volume integrals (extension): un-batched views of BatchedRCWA.volume_integral / absorption_by_region ----
+    def volume_integral(self, layer_num, field="E", components="xyz", weight=None, z_range=None, normalize=False):
+        """[nr] ([R, nr] for a stack of weights [R, nx, ny]): the integral of w |F|^2 over the cell (as a cell average) and the in-layer
+        ranges z_range ([nr, 2]; None: the whole layer) of an internal layer, in closed form (torcwa_amd/volume.py)."""
+        self._flux_source()
+        return self._b.volume_integral(layer_num, field, components, weight, z_range, normalize, _stacked=True)[0]
+
+    def absorption_by_region(self, layer_num, masks=None, z_range=None):
+        """[R, nr] ([nr] for masks=None): the absorbed fraction of the incident flux inside the regions masks [R, nx, ny] and the ranges
+        z_range of an internal layer (torcwa_amd/volume.py)."""
+        self._flux_source()
+        return self._b.absorption_by_region(layer_num, masks, z_range, _stacked=True)[0]
+
     def return_layer(self, layer_num, nx=100, ny=100):                                  # rcwa.py:264-298
         """eps(x,y), mu(x,y) of a layer recovered from the truncated Fourier series held in its convolution matrix.
         Harmonic (i, j), |i| <= 2ox, |j| <= 2oy, is read from the first column / first row of the Toeplitz matrix and
