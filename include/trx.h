@@ -350,13 +350,47 @@ size_t trx_modal_overlap_ws_bytes(int dtype, int n, int nr, int batch);
 int trx_modal_overlap(int dtype, const void* M, const void* cplus, const void* cminus, const void* kz, const double* omega, const double* d,
                       const double* zr, int z_is_fraction, int s, int n, int nr, int batch, void* out, void* ws, size_t ws_bytes, void* stream);
 
+/* ---- mirror-symmetry folding of a layer eigenproblem (no reference counterpart; the reduction S4, RETICOLO and others offer) ---------------
+ * A layer that is invariant under x -> -x about a plane (and / or y -> -y), lit with kx0 = 0 (ky0 = 0), has A = P Q commuting with the mirror
+ * R_x = diag(-J_x, +J_x) on [Ex; Ey] (R_y = diag(+J_y, -J_y)), where J_x sends the unit vector of harmonic (m, n) to exp(+2 pi i m c / nx) times
+ * that of (-m, n); c is the integer with grid[i, j] == grid[(c - i) mod nx, j] (c = nx - 1 for samples at (i + 1/2) h, c = 0 for a grid that is
+ * symmetric about sample 0).  In the basis T of joint eigenvectors of the mirrors A is block diagonal: two blocks of n / 2 for one mirror, four
+ * of about n / 4 for two.  T is unitary and sparse and is handed over as a PLAN in device memory, built once by the caller (never by the kernels):
+ *   idx [n,4] int32   rows of the non-zeros of column j of T (unused slots: any row in [0, n) with weight 0)
+ *   wt  [n,4] `dtype` their values (modulus 1/sqrt(2) or 1/2 or 1)
+ *   off [nblk+1] int32  the columns of T are sorted by block: block k is columns off[k] .. off[k+1]-1, off[0] = 0, off[nblk] = n, 1 <= nblk <= 4
+ * Inside one block the columns of T have disjoint supports (true of any basis built orbit by orbit); trx_sym_unfold relies on it.
+ * Packing of per-block arrays ("packed"): blocks of equal size n_k form a group, groups ordered by their first block; a group of g blocks is one
+ * contiguous [g * batch, n_k, n_k] array (block-major, then batch), ready for ONE trx_eig call per distinct size; eigenvalues likewise as
+ * [g * batch, n_k].  The groups follow each other without padding: sum_k batch n_k^2 (sum_k batch n_k = batch n) elements in all.
+ *
+ * trx_sym_fold: blocks (packed) = the diagonal blocks B_k = T_k^H A T_k of A [batch,n,n] (not modified); resid[batch] (double) = the largest
+ * modulus among the entries of T^H A T OUTSIDE the diagonal blocks, divided by max |A| (0 for A = 0): rounding level when A commutes with the
+ * mirrors, O(1) when it does not.  Separable: C = T^H A along the rows, then C T along the columns, 2 - 4 reads per element and pass.
+ * Traffic model (elements per matrix): 2 n^2 (one mirror) or 4 n^2 (two) read of A, n^2 written and read back for C, sum_k n_k^2 written:
+ * (nblk + 2 + 1 / nblk) n^2 = 4.5 n^2 / 6.25 n^2, i.e. 266 MB / 369 MB per complex128 matrix at n = 1922; no arithmetic to speak of.  Deterministic (exact maxima, combined in a
+ * fixed order; no atomics).  A malformed off (not monotone from 0 to n) writes no block and sets resid to NaN; idx is clamped into [0, n).
+ * ws: trx_sym_fold_ws_bytes = one [batch,n,n] matrix for C and 16 ceil(n/8) batch bytes of partial maxima, 16-byte aligned.
+ * trx_sym_unfold: W [batch,n,n] and lam [batch,n] from the packed eigenvectors Wk and eigenvalues lamk of the blocks (as trx_eig returns them
+ * per group): W[:, off[k]:off[k+1]] = T_k W_k, lam = the block eigenvalues in block order.  T is unitary, so the columns of W keep the unit
+ * 2-norm of trx_eig's geev convention and A W = W diag(lam) holds in the original basis.  W is zero-filled first (rows a block does not reach),
+ * then every element has one writer: 2 n^2 written, sum_k n_k^2 read.  No workspace.
+ * Both: stream-ordered, no host synchronisation; complex64 and complex128; n^2 < 2^31, batch <= 65535, else TRX_ERR_ARG; batch = 0 returns
+ * TRX_OK without touching any buffer.  Element alignment suffices for every buffer but ws. */
+size_t trx_sym_fold_ws_bytes(int dtype, int n, int batch);
+int trx_sym_fold(int dtype, const void* A, int n, int batch, const int* idx, const void* wt, const int* off, int nblk, void* blocks, double* resid,
+                 void* ws, size_t ws_bytes, void* stream);
+int trx_sym_unfold(int dtype, const void* Wk, const void* lamk, int n, int batch, const int* idx, const void* wt, const int* off, int nblk, void* W,
+                   void* lam, void* stream);
+
 /* ---- measurement aid (no reference counterpart): HIP-event timing of the dominant kernels --------------------
  * trx_prof_enable(1) makes the instrumented launch sites record hipEvents on the launch stream.  Sampling is systematic and
  * uniform over the run: every stride-th launch of a tag is timed; when the pool (2048 event pairs per tag) is full every
  * other sample is dropped and the stride doubles.  trx_prof_get(tag, out[7]) waits for those events and returns
  * {launches, timed_launches, algorithmic flops of the timed launches, algorithmic bytes of the timed launches,
  * milliseconds of the timed launches, flops of ALL launches, bytes of ALL launches} (the last two are exact sums, not samples).  Tags: 0 gemm N,N; 1 gemm other ops; 2 QR prepare (AED);
- * 3 QR off-window update; 4 QR window chase; 5 Hessenberg gemv; 6 Hessenberg reflector column; 7 LU panel. */
+ * 3 QR off-window update; 4 QR window chase; 5 Hessenberg gemv; 6 Hessenberg reflector column; 7 LU panel; 8 - 15 see trx_prof_tag_name;
+ * 16 trx_sym_fold (both passes); 17 trx_sym_unfold (zero fill and scatter). */
 int trx_prof_enable(int on);
 int trx_prof_reset(void);
 int trx_prof_get(int tag, double* out);

@@ -8,7 +8,7 @@ built by `python torcwa_amd/csrc/build.py`).  There is no CPU fallback.
 """
 from .torch_eig import Eig
 from .geometry import geometry, lattice_geometry, rcwa_geo
-from . import lattice, materials
+from . import lattice, materials, symmetry
 from .rcwa import rcwa
 from .batched import BatchedRCWA
 from .engine import Engine, NumericalError

@@ -75,6 +75,9 @@ _SIGS = {
     "trx_modal_overlap_ws_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
     "trx_modal_overlap": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int,
                                   c_void_p, c_void_p, c_size_t, c_void_p]),
+    "trx_sym_fold_ws_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "trx_sym_fold": (c_int, [c_int, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "trx_sym_unfold": (c_int, [c_int, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p]),
     "trx_tuning": (c_int, [c_char_p, c_int]),
     "trx_prof_enable": (c_int, [c_int]),
     "trx_prof_reset": (c_int, []),

@@ -15,6 +15,7 @@ import torch
 from .engine import Engine, default_engine
 from . import autograd_ops as ag
 from . import lattice as _lat
+from . import symmetry as _sym
 from .flux import FluxMixin
 from .torch_eig import Eig
 from .volume import VolumeMixin
@@ -84,8 +85,19 @@ def _halfspace_V(kx, ky, epsmu):
 class BatchedRCWA(FluxMixin, VolumeMixin):
     def __init__(self, freq, order, L, *, batch=None, dtype=torch.complex64, device=None, stable_eig_grad=True,
                  avoid_Pinv_instability=False, max_Pinv_instability=0.005, precision="high", engine=None,
-                 keep_coupling=True, fold_layers=False, eig_route="auto", route_hint=None, fourier_rule="laurent", nv_sigma=NV_SIGMA_DEFAULT):
+                 keep_coupling=True, fold_layers=False, eig_route="auto", route_hint=None, fourier_rule="laurent", nv_sigma=NV_SIGMA_DEFAULT,
+                 symmetry=None, symmetry_tol=1e-6):
         check_fourier_rule(fourier_rule)
+        # symmetry (extension): None | "x" | "y" | "xy" -- the caller states that every patterned layer is invariant under x -> -x (y -> -y) about
+        # a plane and that kx0 = 0 (ky0 = 0) at every sweep point.  A = P Q of such a layer is then folded into 2 / 4 independent eigenproblems
+        # (include/trx.h: trx_sym_fold; torcwa_amd/symmetry.py) and the modes are unfolded into the original basis, so nothing downstream changes.
+        # Checked, not trusted: the lattice, the order set, the wave vector and every grid (to symmetry_tol, relative to max |grid|); a grid that is
+        # symmetric only to within the tolerance yields the solution of its symmetrised structure.  None: today's path, untouched.
+        _sym.check_symmetry(symmetry)
+        self.symmetry = symmetry
+        self.symmetry_tol = float(symmetry_tol)
+        self.symmetry_residual = []      # per layer: resid [B] of trx_sym_fold (the discarded part of T^H A T relative to max |A|), or None
+        self._sym_plans = {}
         # fourier_rule="li" needs the rectangular order box on a rectangular lattice (ValueError otherwise, see the order / lattice below).
         # fourier_rule="li": Li's inverse rule for the x / y components of D in every patterned layer (Ex, Ey convolution matrices,
         # include/trx.h trx_convmat_li); Ez / Hz keep Laurent's matrices (E^-1 in P, trx_hmodes, eps_conv).  "laurent": the reference's rule.
@@ -166,6 +178,10 @@ class BatchedRCWA(FluxMixin, VolumeMixin):
         self._mn = mn
         self._mn_dev = self.orders.to(torch.int32).contiguous()
         self._mmax, self._nmax = int(np.abs(mn[:, 0]).max()), int(np.abs(mn[:, 1]).max())
+        if self.symmetry is not None:
+            if not rect_lattice:
+                raise ValueError(f'symmetry="{self.symmetry}" needs a rectangular lattice (the mirrors x -> -x, y -> -y do not map an oblique lattice onto itself)')
+            _sym.check_orders_closed(mn, self.symmetry)
         self._index = {(int(p), int(q)): i for i, (p, q) in enumerate(mn)} if self._general else None
         one = torch.ones(self.B, dtype=self._cdtype, device=self._device)
         self.eps_in, self.mu_in, self.eps_out, self.mu_out = one, one.clone(), one.clone(), one.clone()
@@ -216,6 +232,14 @@ class BatchedRCWA(FluxMixin, VolumeMixin):
             warnings.warn("Invalid angle layer. Set as input layer.", UserWarning)
             self.angle_layer = "input"
         self._kvectors()
+        if self.symmetry is not None:
+            # the mirror x -> -x maps kx0 + m Gx onto -(kx0 + m Gx) only for kx0 = 0 (ky0 is free: an angle sweep in the yz plane qualifies)
+            bad = torch.stack([(k != 0).any() for k, nm in ((self.kx0_norm, "x"), (self.ky0_norm, "y")) if nm in self.symmetry]).cpu().tolist()
+            for flag, nm in zip(bad, [nm for nm in "xy" if nm in self.symmetry]):
+                if flag:
+                    raise ValueError(f'symmetry="{self.symmetry}": k{nm}0_norm must be exactly 0 at every sweep point for the {nm} mirror '
+                                     f"(the incident wave vector must lie in the mirror plane), got max |k{nm}0_norm| = "
+                                     f"{float(torch.abs(self.kx0_norm if nm == 'x' else self.ky0_norm).max()):.3g}")
 
     def _kvectors(self):                                                                # rcwa.py:1124-1181
         em = self.eps_in * self.mu_in if self.angle_layer == "input" else self.eps_out * self.mu_out
@@ -264,6 +288,13 @@ class BatchedRCWA(FluxMixin, VolumeMixin):
         diff = torch.is_grad_enabled() and any(torch.is_tensor(v) and v.requires_grad for v in
                                                (thickness, eps, mu, self.freq, self.Kx_norm_dn, self.Ky_norm_dn))
         self._diff = getattr(self, "_diff", False) or diff
+        if self.symmetry is not None:
+            if self._diff:
+                raise ValueError("symmetry= is not available on a differentiable stack (a tensor of this layer or an earlier one requires grad): "
+                                 "the adjoint of the folded eigenproblem is not implemented")
+            if normal_field is not None:
+                raise ValueError("symmetry= cannot be combined with add_layer(normal_field=...): a caller-supplied field is not checked for the mirror; "
+                                 "let the field be derived from the grid")
 
         def conv(v, homog):
             if homog:
@@ -315,6 +346,7 @@ class BatchedRCWA(FluxMixin, VolumeMixin):
 
         if eps_h and mu_h and not diff and not self.keep_coupling:
             self._add_homogeneous_layer_bd(thickness, self._bvec(eps), self._bvec(mu))
+            self.symmetry_residual.append(None)
             self._fold_last_layer()
             return
         # Sweep drivers (keep_coupling=False) with a homogeneous mu never read P, Q, the dense mu matrices or, after the layer's
@@ -326,6 +358,9 @@ class BatchedRCWA(FluxMixin, VolumeMixin):
             M, Minv, mu_s = None, None, self._bvec(mu)
         else:
             M, Minv, mu_s = conv(mu, mu_h)
+        plan = None
+        if self.symmetry is not None and not (eps_h and mu_h):          # before any heavy work: a grid without the mirror raises here
+            plan = self._sym_plan([torch.as_tensor(v, device=self._device) for v, h in ((eps, eps_h), (mu, mu_h)) if not h])
         li = self.fourier_rule == "li" and not (eps_h and mu_h)
         Ex, Ey = conv_li(eps, eps_h, E) if li else (None, None)
         Mx, My = conv_li(mu, mu_h, M) if (li and M is not None) else (None, None)
@@ -386,10 +421,15 @@ class BatchedRCWA(FluxMixin, VolumeMixin):
                 # Li's / the normal-vector matrices live on only in eps_conv_x / _y / _xx / _xy / _yy (keep_coupling)
                 del Einv, Ex, Ey, Mx, My, Exy
                 # mixed-precision eigensolver: two Newton steps for a complex64 problem (1e-5 gate), three for complex128 (engine.eig)
-                lam, W = self._eig_call(A, refine_steps=3 if self._dtype == torch.complex128 else 2)      # torch_eig.py:14
+                steps = 3 if self._dtype == torch.complex128 else 2
+                if plan is None:
+                    lam, W = self._eig_call(A, refine_steps=steps)                          # torch_eig.py:14
+                else:
+                    lam, W, resid = self._eig_folded(A, plan, steps)
                 del A
             kz = torch.sqrt(lam)
             kz = torch.where(torch.imag(kz) < 0, -kz, kz)                               # rcwa.py:1241
+        self.symmetry_residual.append(resid if plan is not None else None)
         self.P.append(P)
         self.Q.append(Q)
         self.kz_norm.append(kz)
@@ -561,7 +601,7 @@ class BatchedRCWA(FluxMixin, VolumeMixin):
             C[1].append(Cn[1][k] + mm(Cn[0][k], X2))
         return S, C
 
-    def _eig_call(self, A, refine_steps):
+    def _eig_call(self, A, refine_steps, out=None):
         """trx_eig with this solver's route policy.  "fp64" / "mixed": as named.  "auto": the library's mixed-precision route, and -- scoped to THIS
         solver object (or to the one sweep call whose chunks share `route_hint`), never beyond -- once a call had to redo matrices in fp64
         (clusters of close eigenvalues beyond the refinement's exact treatment: symmetric meta-atoms, the dense spectra of large orders), the
@@ -572,10 +612,31 @@ class BatchedRCWA(FluxMixin, VolumeMixin):
         route = {"auto": 0, "mixed": 3, "fp64": 1}[self.eig_route]
         if self.eig_route == "auto" and self._route_hint.get(key):
             route = 1
-        lam, W = eng.eig(A, destroy=True, refine_steps=refine_steps, route=route)
+        lam, W = eng.eig(A, destroy=True, refine_steps=refine_steps, route=route, **({} if out is None else {"out": out}))
         if self.eig_route == "auto" and route == 0 and eng.eig_fallback_of_last_call() > 0:
             self._route_hint[key] = True
         return lam, W
+
+    def _sym_plan(self, grids):
+        """The folding plan of a patterned layer: the centre c of every claimed mirror is detected from the layer's grids (ValueError if a grid
+        does not have the mirror), and the plan of (c, grid size) is built once per solver."""
+        key = _sym.grid_centres(grids, self.symmetry, self.symmetry_tol)
+        if key not in self._sym_plans:
+            self._sym_plans[key] = _sym.build_plan(self._mn, self.symmetry, *key)
+        return self._sym_plans[key]
+
+    def _eig_folded(self, A, plan, refine_steps):
+        """(lam, W, resid) of A through its symmetry blocks: fold, one trx_eig call per distinct block size (the route hint is keyed by size),
+        unfold into the original basis."""
+        eng = self.engine
+        blocks, resid = eng.sym_fold(A, plan)
+        Wp, lp, Wk, lamk = eng.sym_packed(plan, A.shape[0], A.dtype)       # trx_eig writes straight into the buffers trx_sym_unfold reads
+        for Bk, wk, lk in zip(blocks, Wk, lamk):
+            if Bk.shape[-1] > 0:
+                self._eig_call(Bk, refine_steps=refine_steps, out=(lk, wk))
+        del blocks
+        lam, W = eng.sym_unfold(Wp, lp, plan)
+        return lam, W, resid
 
     def _is_homogeneous(self, v):
         if isinstance(v, (float, complex)):

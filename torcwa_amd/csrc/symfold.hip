@@ -1,0 +1,292 @@
+// Mirror-symmetry folding of a layer eigenproblem (include/trx.h: trx_sym_fold, trx_sym_unfold).
+//
+// T is the unitary symmetry-adapted basis of one or two mirrors: column j has at most four non-zeros wt[j][q] in the rows idx[j][q], and the
+// columns are sorted by symmetry class (block k = columns off[k] .. off[k+1]-1).  For A commuting with the mirrors T^H A T is block diagonal.
+//
+//   fold    C = T^H A  (rows_kernel: row j of C is a combination of at most four rows of A, read and written along the rows: coalesced),
+//           D = C T    (cols_kernel: column j of D is a combination of at most four columns of C; the lanes of a wave walk j, so the gathers of
+//                       one row stay inside that row's n elements, and the plan entry of a column is loaded once for SF_ROWS rows);
+//           the entries of D inside a diagonal block go to the packed output, the largest modulus of all the others is the residual.
+//   unfold  W[:, block k] = T_k W_k: row j of W_k, scaled, is written to the at most four rows idx[off[k] + j][q] of W (the supports of the
+//           columns of one block are disjoint, so every element of W has one writer); W is zeroed first for the rows a block does not reach.
+//
+// Traffic model per matrix (elements of `dtype`, the one of include/trx.h, DESIGN.md and the prof tags): fold reads the referenced rows of A once
+// per referencing column (nblk n^2: 2 n^2 for one mirror, 4 n^2 for two, the rows of one orbit sit in different workgroups), writes and re-reads
+// C (2 n^2) and writes sum_k n_k^2 ~ n^2 / nblk: (nblk + 2 + 1 / nblk) n^2 = 4.5 n^2 / 6.25 n^2; unfold writes W twice (zero fill, n^2 each) and
+// reads sum_k n_k^2: (2 + 1 / nblk) n^2.  Both are far below one GEMM of the same size.  Maxima are exact and order-independent;
+// per workgroup one partial goes to the workspace and a second kernel combines them: deterministic, no atomics.
+#include "common.hpp"
+#include "prof.hpp"
+
+using namespace trx;
+
+namespace {
+
+constexpr int SF_THREADS = 256;
+constexpr int SF_ROWS = 8;        // rows of the output per workgroup
+constexpr int SF_MAXBLK = 4;
+
+// Block offsets and the packing of the per-block arrays: blocks of equal size form one group, groups in the order of their first block;
+// a group of g blocks of size s is one contiguous [g, batch, u] region, u = s * s (matrices) or s (eigenvalues).
+struct SymLayout {
+    int off[SF_MAXBLK + 1];
+    long base2[SF_MAXBLK], base1[SF_MAXBLK];   // element offset of (block k, batch entry 0)
+    int ok;
+};
+
+__device__ __forceinline__ SymLayout sym_layout(const int* __restrict__ off, int nblk, int n, int batch) {
+    SymLayout L;
+    L.ok = 1;
+#pragma unroll
+    for (int k = 0; k <= SF_MAXBLK; ++k) L.off[k] = k <= nblk ? off[k] : n;
+    if (L.off[0] != 0 || L.off[nblk] != n) L.ok = 0;
+#pragma unroll
+    for (int k = 0; k < SF_MAXBLK; ++k)
+        if (k < nblk && L.off[k + 1] < L.off[k]) L.ok = 0;
+#pragma unroll
+    for (int k = 0; k < SF_MAXBLK; ++k) {
+        L.base2[k] = L.base1[k] = 0;
+        if (k >= nblk || !L.ok) continue;
+        const long s = L.off[k + 1] - L.off[k];
+        long acc2 = 0, acc1 = 0;
+        for (int f = 0; f < nblk; ++f) {
+            const long sf = L.off[f + 1] - L.off[f];
+            bool first = true;
+            for (int e = 0; e < f; ++e) first = first && (L.off[e + 1] - L.off[e] != sf);
+            if (!first) continue;
+            if (sf == s) {                                   // the group of block k: t blocks of this size come before it
+                long t = 0;
+                for (int e = 0; e < k; ++e) t += (L.off[e + 1] - L.off[e] == s);
+                L.base2[k] = acc2 + t * batch * s * s;
+                L.base1[k] = acc1 + t * batch * s;
+                break;
+            }
+            long g = 0;
+            for (int e = 0; e < nblk; ++e) g += (L.off[e + 1] - L.off[e] == sf);
+            acc2 += g * batch * sf * sf;
+            acc1 += g * batch * sf;
+        }
+    }
+    return L;
+}
+
+__device__ __forceinline__ int block_of(const SymLayout& L, int nblk, int j) {
+    int k = 0;
+#pragma unroll
+    for (int e = 1; e < SF_MAXBLK; ++e) k += (e < nblk && j >= L.off[e]);
+    return k;
+}
+
+template <class T> __device__ __forceinline__ bool nonzero(cx<T> w) { return w.x != T(0) || w.y != T(0); }
+__device__ __forceinline__ int clamp_row(int i, int n) { return i < 0 ? 0 : (i >= n ? n - 1 : i); }
+
+// largest value of the workgroup in thread 0
+__device__ __forceinline__ double block_max(double v) {
+    __shared__ double red[SF_THREADS / 64];
+    v = wave_max(v);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+    __syncthreads();
+    double m = red[0];
+#pragma unroll
+    for (int w = 1; w < SF_THREADS / 64; ++w) m = red[w] > m ? red[w] : m;
+    return m;
+}
+
+// C = T^H A.  grid (ceil(n / SF_ROWS), batch); amax2 [batch, gridDim.x]: largest |A|^2 among the elements read.
+template <class T>
+__global__ __launch_bounds__(SF_THREADS) void sym_rows_kernel(const cx<T>* __restrict__ A, const int* __restrict__ idx, const cx<T>* __restrict__ wt,
+                                                              int n, cx<T>* __restrict__ C, double* __restrict__ amax2) {
+    const int tid = threadIdx.x, b = blockIdx.y, j0 = blockIdx.x * SF_ROWS;
+    const cx<T>* Ab = A + (long)b * n * n;
+    cx<T>* Cb = C + (long)b * n * n;
+    double mx = 0.0;
+    for (int rr = 0; rr < SF_ROWS && j0 + rr < n; ++rr) {
+        const int j = j0 + rr;
+        int s[4];
+        cx<T> w[4];
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            s[q] = clamp_row(idx[j * 4 + q], n);
+            w[q] = conj(wt[j * 4 + q]);
+        }
+        for (int col = tid; col < n; col += SF_THREADS) {
+            cx<T> acc(T(0), T(0));
+#pragma unroll
+            for (int q = 0; q < 4; ++q)
+                if (nonzero(w[q])) {                                                // wave-uniform
+                    const cx<T> a = Ab[(long)s[q] * n + col];
+                    cfma(acc, w[q], a);
+                    const double m = (double)a.x * (double)a.x + (double)a.y * (double)a.y;
+                    mx = m > mx ? m : mx;
+                }
+            Cb[(long)j * n + col] = acc;
+        }
+    }
+    mx = block_max(mx);
+    if (tid == 0) amax2[(long)b * gridDim.x + blockIdx.x] = mx;
+}
+
+// D = C T: diagonal blocks to `blocks`, the largest |D|^2 outside them to omax2 [batch, gridDim.x] (NaN for a malformed plan).
+template <class T>
+__global__ __launch_bounds__(SF_THREADS) void sym_cols_kernel(const cx<T>* __restrict__ C, const int* __restrict__ idx, const cx<T>* __restrict__ wt,
+                                                              const int* __restrict__ off, int nblk, int n, int batch, cx<T>* __restrict__ blocks,
+                                                              double* __restrict__ omax2) {
+    const int tid = threadIdx.x, b = blockIdx.y, r0 = blockIdx.x * SF_ROWS;
+    const SymLayout L = sym_layout(off, nblk, n, batch);
+    const cx<T>* Cb = C + (long)b * n * n;
+    const int rows = n - r0 < SF_ROWS ? n - r0 : SF_ROWS;
+    double mx = 0.0;
+    if (L.ok) {
+        for (int j = tid; j < n; j += SF_THREADS) {
+            int s[4];
+            cx<T> w[4];
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                s[q] = clamp_row(idx[j * 4 + q], n);
+                w[q] = wt[j * 4 + q];
+            }
+            const int kj = block_of(L, nblk, j);
+            const long sj = L.off[kj + 1] - L.off[kj];
+            cx<T>* dst = blocks + L.base2[kj] + (long)b * sj * sj + (j - L.off[kj]);
+            for (int rr = 0; rr < rows; ++rr) {
+                const int r = r0 + rr;
+                const cx<T>* Crow = Cb + (long)r * n;
+                cx<T> acc(T(0), T(0));
+#pragma unroll
+                for (int q = 0; q < 4; ++q)
+                    if (nonzero(w[q])) cfma(acc, Crow[s[q]], w[q]);
+                if (block_of(L, nblk, r) == kj) {
+                    dst[(long)(r - L.off[kj]) * sj] = acc;
+                } else {
+                    const double m = (double)acc.x * (double)acc.x + (double)acc.y * (double)acc.y;
+                    mx = m > mx ? m : mx;
+                }
+            }
+        }
+    }
+    mx = block_max(mx);
+    if (tid == 0) omax2[(long)b * gridDim.x + blockIdx.x] = L.ok ? mx : __builtin_nan("");
+}
+
+// resid[b] = sqrt(max omax2) / sqrt(max amax2)
+__global__ __launch_bounds__(64) void sym_resid_kernel(const double* __restrict__ amax2, const double* __restrict__ omax2, int groups, int batch,
+                                                       double* __restrict__ resid) {
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= batch) return;
+    double a = 0.0, o = 0.0;
+    bool bad = false;
+    for (int g = 0; g < groups; ++g) {
+        const double va = amax2[(long)b * groups + g], vo = omax2[(long)b * groups + g];
+        bad = bad || va != va || vo != vo;
+        a = va > a ? va : a;
+        o = vo > o ? vo : o;
+    }
+    resid[b] = bad ? __builtin_nan("") : (a > 0.0 ? sqrt(o) / sqrt(a) : 0.0);
+}
+
+// W[idx[J][q], off[k] + c] = wt[J][q] Wk[j, c] for column J = off[k] + j of T; lam[J] = lamk[j].  grid (ceil(n / SF_ROWS), batch); W zeroed before.
+template <class T>
+__global__ __launch_bounds__(SF_THREADS) void sym_unfold_kernel(const cx<T>* __restrict__ Wk, const cx<T>* __restrict__ lamk, const int* __restrict__ idx,
+                                                                const cx<T>* __restrict__ wt, const int* __restrict__ off, int nblk, int n, int batch,
+                                                                cx<T>* __restrict__ W, cx<T>* __restrict__ lam) {
+    const int tid = threadIdx.x, b = blockIdx.y, J0 = blockIdx.x * SF_ROWS;
+    const SymLayout L = sym_layout(off, nblk, n, batch);
+    if (!L.ok) return;
+    cx<T>* Wb = W + (long)b * n * n;
+    for (int rr = 0; rr < SF_ROWS && J0 + rr < n; ++rr) {
+        const int J = J0 + rr;
+        const int k = block_of(L, nblk, J);
+        const long s = L.off[k + 1] - L.off[k];
+        const int j = J - L.off[k];
+        const cx<T>* src = Wk + L.base2[k] + (long)b * s * s + (long)j * s;
+        int rw[4];
+        cx<T> w[4];
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            rw[q] = clamp_row(idx[J * 4 + q], n);
+            w[q] = wt[J * 4 + q];
+        }
+        for (int c = tid; c < (int)s; c += SF_THREADS) {
+            const cx<T> v = src[c];
+#pragma unroll
+            for (int q = 0; q < 4; ++q)
+                if (nonzero(w[q])) Wb[(long)rw[q] * n + L.off[k] + c] = w[q] * v;
+        }
+        if (tid == 0) lam[(long)b * n + J] = lamk[L.base1[k] + (long)b * s + j];
+    }
+}
+
+size_t part_bytes(int n, int batch) { return sizeof(double) * 2 * (size_t)cdiv_i(n, SF_ROWS) * (size_t)batch; }
+
+template <class T>
+int sym_fold_t(hipStream_t st, const cx<T>* A, int n, int batch, const int* idx, const cx<T>* wt, const int* off, int nblk, cx<T>* blocks,
+               double* resid, char* ws) {
+    const int groups = cdiv_i(n, SF_ROWS);
+    double* amax2 = (double*)ws;
+    double* omax2 = amax2 + (size_t)groups * batch;
+    cx<T>* C = (cx<T>*)(ws + ((part_bytes(n, batch) + 15) & ~(size_t)15));
+    const double nn = (double)n * n * batch;
+    ProfScope prof(PROF_SYM_FOLD, st, 8.0 * 8.0 * nn, sizeof(cx<T>) * (nblk + 2.0 + 1.0 / nblk) * nn);   // A once per referencing column, C out and in, blocks
+    const dim3 grid(groups, batch);
+    TRX_LAUNCH((sym_rows_kernel<T>), grid, dim3(SF_THREADS), 0, st, A, idx, wt, n, C, amax2);
+    TRX_CHECK_LAUNCH();
+    TRX_LAUNCH((sym_cols_kernel<T>), grid, dim3(SF_THREADS), 0, st, (const cx<T>*)C, idx, wt, off, nblk, n, batch, blocks, omax2);
+    TRX_CHECK_LAUNCH();
+    TRX_LAUNCH(sym_resid_kernel, dim3(cdiv_i(batch, 64)), dim3(64), 0, st, (const double*)amax2, (const double*)omax2, groups, batch, resid);
+    TRX_CHECK_LAUNCH();
+    return TRX_OK;
+}
+
+template <class T>
+int sym_unfold_t(hipStream_t st, const cx<T>* Wk, const cx<T>* lamk, int n, int batch, const int* idx, const cx<T>* wt, const int* off, int nblk,
+                 cx<T>* W, cx<T>* lam) {
+    const double nn = (double)n * n * batch;
+    ProfScope prof(PROF_SYM_UNFOLD, st, 0.0, sizeof(cx<T>) * (2.0 + 1.0 / (nblk > 0 ? nblk : 1)) * nn);
+    if (hipMemsetAsync(W, 0, sizeof(cx<T>) * (size_t)n * n * batch, st) != hipSuccess) return TRX_ERR_LAUNCH;
+    TRX_LAUNCH((sym_unfold_kernel<T>), dim3(cdiv_i(n, SF_ROWS), batch), dim3(SF_THREADS), 0, st, Wk, lamk, idx, wt, off, nblk, n, batch, W, lam);
+    TRX_CHECK_LAUNCH();
+    return TRX_OK;
+}
+
+int check_common(int dtype, int n, int batch, int nblk) {
+    if (dtype != TRX_C64 && dtype != TRX_C128) return TRX_ERR_DTYPE;
+    if (n < 1 || batch < 0 || batch > 65535 || nblk < 1 || nblk > SF_MAXBLK) return TRX_ERR_ARG;
+    if ((size_t)n * (size_t)n >= ((size_t)1 << 31)) return TRX_ERR_ARG;            // 4 n stays inside int as well
+    return TRX_OK;
+}
+
+}  // namespace
+
+extern "C" size_t trx_sym_fold_ws_bytes(int dtype, int n, int batch) {
+    if (n < 0 || batch < 0 || (dtype != TRX_C64 && dtype != TRX_C128)) return 0;
+    const size_t el = dtype == TRX_C128 ? 16 : 8;
+    return ((part_bytes(n, batch) + 15) & ~(size_t)15) + el * (size_t)n * (size_t)n * (size_t)batch;
+}
+
+extern "C" int trx_sym_fold(int dtype, const void* A, int n, int batch, const int* idx, const void* wt, const int* off, int nblk, void* blocks,
+                            double* resid, void* ws, size_t ws_bytes, void* stream) {
+    const int rc = check_common(dtype, n, batch, nblk);
+    if (rc != TRX_OK) return rc;
+    if (batch == 0) return TRX_OK;
+    if (!A || !idx || !wt || !off || !blocks || !resid || !ws) return TRX_ERR_ARG;
+    if ((size_t)ws & 15) return TRX_ERR_ARG;
+    if (ws_bytes < trx_sym_fold_ws_bytes(dtype, n, batch)) return TRX_ERR_WORKSPACE;
+    hipStream_t st = trx::api_stream(stream);
+    if (dtype == TRX_C64)
+        return sym_fold_t<float>(st, (const cx<float>*)A, n, batch, idx, (const cx<float>*)wt, off, nblk, (cx<float>*)blocks, resid, (char*)ws);
+    return sym_fold_t<double>(st, (const cx<double>*)A, n, batch, idx, (const cx<double>*)wt, off, nblk, (cx<double>*)blocks, resid, (char*)ws);
+}
+
+extern "C" int trx_sym_unfold(int dtype, const void* Wk, const void* lamk, int n, int batch, const int* idx, const void* wt, const int* off, int nblk,
+                              void* W, void* lam, void* stream) {
+    const int rc = check_common(dtype, n, batch, nblk);
+    if (rc != TRX_OK) return rc;
+    if (batch == 0) return TRX_OK;
+    if (!Wk || !lamk || !idx || !wt || !off || !W || !lam) return TRX_ERR_ARG;
+    hipStream_t st = trx::api_stream(stream);
+    if (dtype == TRX_C64)
+        return sym_unfold_t<float>(st, (const cx<float>*)Wk, (const cx<float>*)lamk, n, batch, idx, (const cx<float>*)wt, off, nblk, (cx<float>*)W,
+                                   (cx<float>*)lam);
+    return sym_unfold_t<double>(st, (const cx<double>*)Wk, (const cx<double>*)lamk, n, batch, idx, (const cx<double>*)wt, off, nblk, (cx<double>*)W,
+                                (cx<double>*)lam);
+}

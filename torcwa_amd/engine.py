@@ -314,7 +314,7 @@ class Engine:
 
     # -- a7 --------------------------------------------------------------------------------------------
     @_phase("eigendecomposition (trx_eig)")
-    def eig(self, A, destroy=False, refine_steps=0, route=0):
+    def eig(self, A, destroy=False, refine_steps=0, route=0, out=None):
         """(w [B,n], V [B,n,n]) with A V = V diag(w) (torcwa/torch_eig.py:14).
 
         refine_steps: Newton steps of libtrx's mixed-precision route (complex128 input of at least 256 rows: fp32 eigendecomposition
@@ -323,7 +323,8 @@ class Engine:
         max |E| ~ 2e-2 ... 2e-1 there).
         route: 0 = the library's automatic choice (mixed precision for complex128 input with n >= 256 and batch >= 8), 1 = all-fp64 (all-fp32 for
         complex64 input), 3 = mixed wherever n >= 8 (include/trx.h "eig_vec").  After the call `eig_fallback_of_last_call()` gives the number of
-        matrices the mixed route redid in fp64 (per calling thread)."""
+        matrices the mixed route redid in fp64 (per calling thread).
+        out: optional (w, V) contiguous tensors of the result's shapes to write into (e.g. slices of the packed buffer of sym_packed)."""
         self._check(A)
         if int(route) not in (0, 1, 3):
             raise ValueError("eig route must be 0 (automatic), 1 (one precision) or 3 (mixed); 2 was the removed inverse-iteration route")
@@ -333,8 +334,14 @@ class Engine:
         A = self._c(A) if destroy else A.clone()
         B, n, _ = A.shape
         dt = A.dtype
-        w = torch.empty((B, n), dtype=dt, device=self.device)
-        V = torch.empty((B, n, n), dtype=dt, device=self.device)
+        if out is None:
+            w = torch.empty((B, n), dtype=dt, device=self.device)
+            V = torch.empty((B, n, n), dtype=dt, device=self.device)
+        else:
+            w, V = out
+            self._check(A, w, V)
+            if tuple(w.shape) != (B, n) or tuple(V.shape) != (B, n, n) or not (w.is_contiguous() and V.is_contiguous()):
+                raise ValueError(f"eig: out must be contiguous ([{B}, {n}], [{B}, {n}, {n}]), got {list(w.shape)} and {list(V.shape)}")
         info = self._ints(B)
         nws = self.lib.eig_ws_bytes_opts(_CODE[dt], n, B, opts)
         ws = self._ws(nws)
@@ -611,6 +618,75 @@ class Engine:
                                               d.data_ptr(), zr.data_ptr(), int(bool(z_is_fraction)), int(s), n, nr, B, out.data_ptr(), ws.data_ptr(),
                                               nws, self.stream))
         return out
+
+    # -- mirror-symmetry folding ------------------------------------------------------------------------
+    @_phase("symmetry fold (trx_sym_fold)")
+    def sym_fold(self, A, plan):
+        """Diagonal blocks of T^H A T for A [B,n,n] and a torcwa_amd.symmetry.SymPlan (include/trx.h: trx_sym_fold).  Returns (blocks, resid):
+        blocks = one [g * B, s, s] tensor per group of plan.groups (views of one packed buffer; block-major, then batch), resid [B] float64 = the
+        largest discarded entry relative to max |A|.  A is not modified."""
+        A = self._c(A)
+        self._check(A)
+        B, n, _ = A.shape
+        if n != plan.n:
+            raise ValueError(f"sym_fold: A is {n} x {n}, the plan is for n = {plan.n}")
+        dt = A.dtype
+        idx, wt, off = plan.device(self.device, dt)
+        packed = torch.empty(B * sum(s * s for s in plan.sizes), dtype=dt, device=self.device)
+        resid = torch.empty(B, dtype=torch.float64, device=self.device)
+        nws = self.lib.sym_fold_ws_bytes(_CODE[dt], n, B)
+        ws = self._ws(nws)
+        self.lib.check(self.lib.sym_fold(_CODE[dt], A.data_ptr(), n, B, idx.data_ptr(), wt.data_ptr(), off.data_ptr(), plan.nblk, packed.data_ptr(),
+                                         resid.data_ptr(), ws.data_ptr(), nws, self.stream))
+        blocks, at = [], 0
+        for s, ks in plan.groups:
+            cnt = len(ks) * B * s * s
+            blocks.append(packed[at:at + cnt].view(len(ks) * B, s, s))
+            at += cnt
+        return blocks, resid
+
+    def sym_packed(self, plan, B, dtype):
+        """Empty packed buffers for the eigenpairs of the blocks of B matrices: (Wp, lp, Wk, lamk) -- the flat buffers trx_sym_unfold reads and
+        their per-group views ([g * B, s, s], [g * B, s]) in the order of plan.groups, to be filled in place (eig(..., out=(lamk[i], Wk[i])))."""
+        Wp = torch.empty(B * sum(s * s for s in plan.sizes), dtype=dtype, device=self.device)
+        lp = torch.empty(B * plan.n, dtype=dtype, device=self.device)
+        Wk, lamk, a2, a1 = [], [], 0, 0
+        for s, ks in plan.groups:
+            g = len(ks) * B
+            Wk.append(Wp[a2:a2 + g * s * s].view(g, s, s))
+            lamk.append(lp[a1:a1 + g * s].view(g, s))
+            a2, a1 = a2 + g * s * s, a1 + g * s
+        return Wp, lp, Wk, lamk
+
+    @_phase("symmetry unfold (trx_sym_unfold)")
+    def sym_unfold(self, Wk, lamk, plan):
+        """(lam [B,n], W [B,n,n]) in the original basis from the eigenvectors and eigenvalues of the blocks (include/trx.h: trx_sym_unfold):
+        W[:, block k] = T_k W_k.  Wk, lamk: the flat packed buffers of sym_packed (read in place, no copy), or lists with one [g * B, s, s] /
+        [g * B, s] tensor per group of plan.groups (packed here: one extra copy of sum_k n_k^2 elements)."""
+        n = plan.n
+        if torch.is_tensor(Wk):
+            self._check(Wk, lamk)
+            dt = Wk.dtype
+            B = lamk.numel() // n
+            if Wk.dim() != 1 or lamk.dim() != 1 or lamk.numel() != B * n or Wk.numel() != B * sum(s * s for s in plan.sizes):
+                raise ValueError("sym_unfold: packed Wk / lamk must be the flat buffers of sym_packed")
+            Wp, lp = self._c(Wk), self._c(lamk)
+        else:
+            self._check(*Wk, *lamk)
+            dt = Wk[0].dtype
+            B = Wk[0].shape[0] // len(plan.groups[0][1])
+            for (s, ks), w, l in zip(plan.groups, Wk, lamk):
+                if tuple(w.shape) != (len(ks) * B, s, s) or tuple(l.shape) != (len(ks) * B, s):
+                    raise ValueError(f"sym_unfold: group of {len(ks)} blocks of size {s} needs [{len(ks) * B}, {s}, {s}] and [{len(ks) * B}, {s}], "
+                                     f"got {list(w.shape)} and {list(l.shape)}")
+            Wp = torch.cat([w.reshape(-1) for w in Wk])
+            lp = torch.cat([l.reshape(-1) for l in lamk])
+        idx, wt, off = plan.device(self.device, dt)
+        W = torch.empty((B, n, n), dtype=dt, device=self.device)
+        lam = torch.empty((B, n), dtype=dt, device=self.device)
+        self.lib.check(self.lib.sym_unfold(_CODE[dt], Wp.data_ptr(), lp.data_ptr(), n, B, idx.data_ptr(), wt.data_ptr(), off.data_ptr(), plan.nblk,
+                                           W.data_ptr(), lam.data_ptr(), self.stream))
+        return lam, W
 
 
 _default = None

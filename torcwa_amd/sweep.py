@@ -79,11 +79,12 @@ def rectangle_density(nx, ny, Lx, Ly, Wx, Wy, Cx, Cy, theta=0.0, edge_sharpness=
 
 def _solve_chunk(freq, layers, order, L, eps_in, eps_out, inc_ang, azi_ang, dtype, precision, engine, orders,
                  polarization, direction, port, check_info, eig_route="auto", route_hint=None, fourier_rule="laurent", nv_sigma=NV_SIGMA_DEFAULT,
-                 absorption=False, source=None):
+                 absorption=False, source=None, symmetry=None, symmetry_tol=1e-6):
     """layers: list of (thickness, eps[, mu]); thickness scalar or [b]; eps/mu scalar, [b] or [b,nx,ny].  absorption: the chunk keeps W, V and
     the coupling matrices (keep_coupling=True, no streaming cascade) and returns (S-parameters, BatchedRCWA.absorption())."""
     sim = BatchedRCWA(freq, order, L, dtype=dtype, precision=precision, engine=engine, keep_coupling=bool(absorption), fold_layers=not absorption,
-                      eig_route=eig_route, route_hint=route_hint, fourier_rule=fourier_rule, nv_sigma=nv_sigma)
+                      eig_route=eig_route, route_hint=route_hint, fourier_rule=fourier_rule, nv_sigma=nv_sigma,
+                      symmetry=symmetry, symmetry_tol=symmetry_tol)
     if eps_in is not None:
         sim.add_input_layer(eps=eps_in)
     if eps_out is not None:
@@ -180,7 +181,7 @@ def _source_amplitudes(source, B):
 def solve_stack_sweep(freq, layers, order, L, *, eps_in=None, eps_out=None, inc_ang=0.0, azi_ang=0.0, dtype=torch.complex64,
                       precision="high", engine=None, chunk=None, streams=1, orders=((0, 0),), polarization="xx",
                       direction="forward", port="transmission", check_info=True, eig_route="auto", fourier_rule="laurent",
-                      nv_sigma=NV_SIGMA_DEFAULT, absorption=False, source=None):
+                      nv_sigma=NV_SIGMA_DEFAULT, absorption=False, source=None, symmetry=None, symmetry_tol=1e-6):
     """B sweep points of a multi-layer stack (BASELINE.json configs 2-4): the reference's per-point Python loop
     (example/Example1-1.ipynb, Example3.ipynb) as chunks of a batched solve.  `layers` as in `_solve_chunk`, with
     per-point quantities carrying a leading dimension B = len(freq).  Returns the requested S-parameter [B, len(orders)].
@@ -190,6 +191,10 @@ def solve_stack_sweep(freq, layers, order, L, *, eps_in=None, eps_out=None, inc_
 
     fourier_rule: "laurent" (default), "li" (Li's inverse rule in every patterned layer, BatchedRCWA) or "normal" (the normal-vector method,
     the field derived from each grid with a Gaussian of nv_sigma cells).
+
+    symmetry: None | "x" | "y" | "xy" -- mirror planes of every patterned layer (kx0 = 0 / ky0 = 0 at every point); each layer eigenproblem is
+    folded into 2 / 4 independent blocks (BatchedRCWA, torcwa_amd/symmetry.py).  ValueError from the first chunk if a grid, the order set, the
+    lattice or an angle does not have the mirror; symmetry_tol: the relative grid asymmetry that is accepted (and symmetrised away).
 
     absorption=True: every chunk is solved with keep_coupling=True and without the streaming cascade (more HBM per point: auto_chunk), the source
     is applied -- `source`: keywords of BatchedRCWA.source_planewave, or of source_fourier when it has "orders"; default a unit plane wave,
@@ -222,7 +227,8 @@ def solve_stack_sweep(freq, layers, order, L, *, eps_in=None, eps_out=None, inc_
         outs[i] = _solve_chunk(freq[lo:hi], lays, order, L, _slice(eps_in, lo, hi, B), _slice(eps_out, lo, hi, B), _slice(inc_ang, lo, hi, B),
                                _slice(azi_ang, lo, hi, B), dtype, precision, engine, orders, polarization, direction, port, check_info,
                                eig_route=eig_route, route_hint=route_hint, fourier_rule=fourier_rule, nv_sigma=nv_sigma,
-                               **({"absorption": True, "source": src} if absorption else {}))
+                               **({"absorption": True, "source": src} if absorption else {}),
+                               symmetry=symmetry, symmetry_tol=symmetry_tol)
 
     dev = freq.device
     try:
