@@ -383,6 +383,51 @@ int trx_sym_fold(int dtype, const void* A, int n, int batch, const int* idx, con
 int trx_sym_unfold(int dtype, const void* Wk, const void* lamk, int n, int batch, const int* idx, const void* wt, const int* off, int nblk, void* W,
                    void* lam, void* stream);
 
+/* ---- thickness sweeps that reuse a layer's modes (no reference counterpart; what modal solvers offer as a layer-thickness scan) ----------------
+ * The modes W, kz, V of a layer do not depend on its thickness d, only the diagonal phase X = exp(i omega kz d) does.  With F = Vf^-1 V (the
+ * 2x2-block-diagonal Vf^-1 of trx_layer_smatrix), A = W + F, B = W - F, mode amplitudes c+ referenced to the layer's left interface and c- to
+ * its right one, the amplitudes in the free-space gaps next to the layer are
+ *   left:  f = (A c+ + B X c-)/2,  r = (B c+ + A X c-)/2        right:  f' = (A X c+ + B c-)/2,  r' = (B X c+ + A c-)/2.
+ * Lft = the cascade of everything left of the layer (input half-space * earlier layers), Rgt = everything right of it, blocks in the order
+ * [S11, S21, S12, S22] as everywhere in this header; R_L = Lft12, R_R = Rgt21.
+ * Operands.  Each side is given as (kind, pointer): kind 0 = absent (the identity S-matrix; pointer ignored), 1 = block diagonal: a device
+ * array bd [4,4,batch,N] as trx_redheffer_halfspace takes it, 2 = dense: a HOST array of 4 device pointers, each [batch,n,n].
+ *
+ * trx_thickness_prepare (once per point; nothing in it depends on the thickness):
+ *   AB [2,batch,n,n] = A | B;   P_L = A - R_L B,  rhoL = P_L^-1 (R_L A - B);   P_R = A - R_R B,  rhoR = P_R^-1 (R_R A - B)      [batch,n,n]
+ *   (the products with R are O(n^2) row combinations for kind 1, one GEMM each for kind 2, absent for kind 0), one LU and an n-column solve per
+ *   side; and for the m requested columns e_c, cols: HOST array of m indices in [0, 2N), 1 <= m <= 16, shared by the batch:
+ *   src [2,batch,n,m]:  src[0] = P_L^-1 2 Lft11 e_c,  src[1] = Lft21 e_c   (direction 0, forward incidence)
+ *                       src[0] = P_R^-1 2 Rgt22 e_c,  src[1] = Rgt12 e_c   (direction 1, backward incidence)
+ *   W, V [batch,n,n] (E_eigvec, H_eigvec), vfinv [4,batch,N] as trx_layer_smatrix.  piv: int[batch*n]; info: int[2*batch], slots 0..batch-1 the
+ *   LU of P_L, batch..2 batch-1 that of P_R (non-zero: singular, that point's outputs are not finite).  ws: trx_thickness_prepare_ws_bytes = one
+ *   [batch,n,n] matrix.  Cost: 2.67 n^3 complex MACs per point (+ 2 n^3 per dense side).  Traffic of the new kernels, elements per point:
+ *   A | B: 2 n^2 read (W, V), 2 n^2 written; P and the right-hand side of one side: 2 n^2 read, 2 n^2 written; the columns O(n m).
+ *
+ * trx_thickness_columns (per chunk of T thicknesses): out[b,t,:,q] = column cols[q] of the block of Lft * layer(d_t) * Rgt that
+ *   (direction, port) reads -- port 0 = transmission, 1 = reflection: blocks S11, S21 for direction 0 and S22, S12 for direction 1 -- i.e. what
+ *   trx_redheffer_halfspace_columns returns for a stack rebuilt at each thickness.  phase [batch,ldt,n] = exp(i omega kz d_t), |phase| <= 1.
+ *   direction 0:  K = I - (rhoL X)(rhoR X),  c+ = K^-1 src[0],  c- = rhoR X c+;   direction 1:  K = I - (rhoR X)(rhoL X),  c- = K^-1 src[0],
+ *   c+ = rhoL X c-;   transmission = Rgt11 f' (direction 0) / Lft22 r (1);   reflection = src[1] + Lft22 r (0) / src[1] + Rgt11 f' (1).
+ *   Per (point, thickness): X rho X and K = I in one elementwise pass (rho read once per point for all T), one GEMM with the other rho shared
+ *   over t (batch stride 0), one LU of K, an m-column solve, skinny products: 1.33 n^3 complex MACs.  direction, m and the operands must be
+ *   those of the prepare call.  ldt >= T: the leading dimension of the thickness axis of phase, out [batch,ldt,n,m] and info [batch,ldt], so a
+ *   caller that chunks T passes pointers offset by t0 (phase + t0 n, out + t0 n m, info + t0) and the arrays' full T as ldt.
+ *   info[b,t]: the LU of K (non-zero: singular K, that entry's columns are not finite).  piv: int[batch*T*(n+1)] scratch.
+ *   ws: trx_thickness_columns_ws_bytes = batch T (2 n^2 + 5 n m) elements; it scales with T: the caller chunks T.  batch * T <= 65535.
+ *   Traffic of the new kernels, elements: K assembly n^2 read per point, 2 n^2 written per (point, thickness); the skinny products read their
+ *   one or two n x n matrices ceil(T m / 8) times per point; everything else is O(n m) per (point, thickness).
+ * Both: stream-ordered, no host synchronisation; complex64 and complex128; batch <= 65535; batch = 0 (and T = 0) returns TRX_OK without touching
+ * any buffer; TRX_ERR_ARG for a kind, direction, port, column index or m out of range or a missing pointer, TRX_ERR_WORKSPACE for a short ws. */
+size_t trx_thickness_prepare_ws_bytes(int dtype, int N, int batch);
+int trx_thickness_prepare(int dtype, const void* W, const void* V, const void* vfinv, int left_kind, const void* left, int right_kind,
+                          const void* right, int direction, const int* cols, int m, int N, int batch, void* rhoL, void* rhoR, void* src, void* AB,
+                          int* piv, int* info, void* ws, size_t ws_bytes, void* stream);
+size_t trx_thickness_columns_ws_bytes(int dtype, int N, int batch, int T, int m);
+int trx_thickness_columns(int dtype, const void* rhoL, const void* rhoR, const void* src, const void* AB, const void* phase, int ldt, int T,
+                          int direction, int port, int left_kind, const void* left, int right_kind, const void* right, int m, int N, int batch,
+                          void* out, int* piv, int* info, void* ws, size_t ws_bytes, void* stream);
+
 /* ---- measurement aid (no reference counterpart): HIP-event timing of the dominant kernels --------------------
  * trx_prof_enable(1) makes the instrumented launch sites record hipEvents on the launch stream.  Sampling is systematic and
  * uniform over the run: every stride-th launch of a tag is timed; when the pool (2048 event pairs per tag) is full every
@@ -390,7 +435,8 @@ int trx_sym_unfold(int dtype, const void* Wk, const void* lamk, int n, int batch
  * {launches, timed_launches, algorithmic flops of the timed launches, algorithmic bytes of the timed launches,
  * milliseconds of the timed launches, flops of ALL launches, bytes of ALL launches} (the last two are exact sums, not samples).  Tags: 0 gemm N,N; 1 gemm other ops; 2 QR prepare (AED);
  * 3 QR off-window update; 4 QR window chase; 5 Hessenberg gemv; 6 Hessenberg reflector column; 7 LU panel; 8 - 15 see trx_prof_tag_name;
- * 16 trx_sym_fold (both passes); 17 trx_sym_unfold (zero fill and scatter). */
+ * 16 trx_sym_fold (both passes); 17 trx_sym_unfold (zero fill and scatter); 18 trx_thickness_prepare (whole call); 19 - 21 the stages of
+ * trx_thickness_columns, one event pair per call each: 19 K assembly and its GEMMs, 20 LU of K and the column solve, 21 amplitudes and read-out. */
 int trx_prof_enable(int on);
 int trx_prof_reset(void);
 int trx_prof_get(int tag, double* out);

@@ -11,9 +11,10 @@ from .geometry import geometry, lattice_geometry, rcwa_geo
 from . import lattice, materials, symmetry
 from .rcwa import rcwa
 from .batched import BatchedRCWA
+from .sweep import solve_thickness_sweep
 from .engine import Engine, NumericalError
 from ._lib import TrxError
 
 __version__ = "0.1.0"
-__all__ = ["Eig", "geometry", "lattice_geometry", "rcwa_geo", "rcwa", "BatchedRCWA", "Engine", "NumericalError", "TrxError", "lattice",
+__all__ = ["Eig", "geometry", "lattice_geometry", "rcwa_geo", "rcwa", "BatchedRCWA", "solve_thickness_sweep", "Engine", "NumericalError", "TrxError", "lattice",
            "materials", "__version__"]

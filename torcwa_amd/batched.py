@@ -133,6 +133,12 @@ class BatchedRCWA(FluxMixin, VolumeMixin):
         self.fold_layers = bool(fold_layers) and not keep_coupling
         self._running = None
         self._n_folded = 0            # layers 0 .. _n_folded-1 live in _running; the rest are stored layers
+        # add_layer(..., swept=True): the one layer whose thickness is a sweep axis [B, T].  It keeps its modes W, kz, V, forms no layer S-matrix
+        # and is not folded; the layers after it fold into a running product of their own (fold_layers).  None: today's paths, untouched.
+        self._swept = None            # dict(index, d [B,T])
+        self._right_running = None
+        self._n_right_folded = 0
+        self.thickness_chunk = None   # thicknesses per library call of a swept solve (None: as many as the free HBM holds, sweep.auto_thickness_chunk)
 
         if batch is None:
             batch = freq.numel() if (torch.is_tensor(freq) and freq.dim() > 0) else (len(freq) if isinstance(freq, (list, tuple)) else 1)
@@ -273,11 +279,23 @@ class BatchedRCWA(FluxMixin, VolumeMixin):
             self._Sout = [(T @ self._Vf).scale(2), T @ D, -(T @ D), (T @ self._Vo).scale(2)]
 
     # ---- a4-a8 -------------------------------------------------------------------------------------------
-    def add_layer(self, thickness, eps=1., mu=1., normal_field=None):                  # rcwa.py:146-170
+    def add_layer(self, thickness, eps=1., mu=1., normal_field=None, *, swept=False):  # rcwa.py:146-170
         """normal_field (fourier_rule="normal" only): (Nx, Ny), each [nx, ny] or [B, nx, ny] on the eps grid, a caller-supplied in-plane field
         for the normal-vector method (e.g. the analytic radial field of a disk), used as given (not normalised) and treated as constant by
-        autograd.  None: the field is derived from the eps grid (trx_normal_field, nv_sigma)."""
+        autograd.  None: the field is derived from the eps grid (trx_normal_field, nv_sigma).
+        swept=True: `thickness` is a sweep axis, [T] (shared by the points) or [B, T].  The layer's modes are computed once, exactly as for a
+        plain layer, and solve_S_parameters returns [B, T, len(orders)] (one GEMM and one LU per thickness, include/trx.h:
+        trx_thickness_prepare / trx_thickness_columns).  At most one swept layer; needs keep_coupling=False and a non-differentiable stack."""
         eng, N, B, cdt = self.engine, self.order_N, self.B, self._cdtype
+        if swept:
+            if self._swept is not None:
+                raise ValueError(f"add_layer(swept=True): layer {self._swept['index']} is already swept; one swept layer per solver "
+                                 "(two thickness axes would need a K per pair of thicknesses)")
+            if self.keep_coupling:
+                raise ValueError("add_layer(swept=True) needs keep_coupling=False: the coupling matrices of a stack depend on the thickness, "
+                                 "and a swept solve keeps none")
+            if self.avoid_Pinv_instability:
+                raise ValueError("add_layer(swept=True) is not available with avoid_Pinv_instability=True (the swept layer takes V = P^-1 W Kz only)")
         eps_h, mu_h = self._is_homogeneous(eps), self._is_homogeneous(mu)
         if normal_field is not None and self.fourier_rule != "normal":
             raise ValueError('add_layer(normal_field=...) needs fourier_rule="normal"')
@@ -288,6 +306,9 @@ class BatchedRCWA(FluxMixin, VolumeMixin):
         diff = torch.is_grad_enabled() and any(torch.is_tensor(v) and v.requires_grad for v in
                                                (thickness, eps, mu, self.freq, self.Kx_norm_dn, self.Ky_norm_dn))
         self._diff = getattr(self, "_diff", False) or diff
+        if (swept or self._swept is not None) and self._diff:
+            raise ValueError("swept=True is not available on a differentiable stack (a tensor of this layer or another one requires grad): "
+                             "the adjoint of the thickness sweep is not implemented")
         if self.symmetry is not None:
             if self._diff:
                 raise ValueError("symmetry= is not available on a differentiable stack (a tensor of this layer or an earlier one requires grad): "
@@ -344,7 +365,7 @@ class BatchedRCWA(FluxMixin, VolumeMixin):
                 return self._nv_tensor_torch(g, nn)
             return eng.convmat_nv(g, self.order[0], self.order[1], cdt, sigma=self.nv_sigma, hx=hx, hy=hy, nn=nn)
 
-        if eps_h and mu_h and not diff and not self.keep_coupling:
+        if eps_h and mu_h and not diff and not self.keep_coupling and not swept:
             self._add_homogeneous_layer_bd(thickness, self._bvec(eps), self._bvec(mu))
             self.symmetry_residual.append(None)
             self._fold_last_layer()
@@ -380,8 +401,17 @@ class BatchedRCWA(FluxMixin, VolumeMixin):
         self.eps_conv_xy.append(Exy if keep_nv else None)
         self.eps_conv_yy.append(Ey if keep_nv else None)
         self.layer_N += 1
-        d = self._bvec(thickness, self._rdtype)
-        self.thickness.append(d)
+        if swept:
+            d = torch.as_tensor(thickness, dtype=self._rdtype, device=self._device)
+            if d.dim() == 1:
+                d = d[None, :].expand(B, -1)
+            if d.dim() != 2 or d.shape[0] != B:
+                raise ValueError(f"add_layer(swept=True): thickness must be [T] or [{B}, T], got {list(d.shape)}")
+            self._swept = dict(index=self.layer_N - 1, d=d.contiguous())
+            self.thickness.append(None)          # no single thickness: see _swept["d"]
+        else:
+            d = self._bvec(thickness, self._rdtype)
+            self.thickness.append(d)
         kxd, kyd = self.Kx_norm_dn, self.Ky_norm_dn
         inv = (lambda A: ag.InverseFn.apply(A, eng)) if diff else eng.inverse
         if Einv is None:
@@ -435,6 +465,9 @@ class BatchedRCWA(FluxMixin, VolumeMixin):
         self.kz_norm.append(kz)
         self.E_eigvec.append(W)
         self._mu_scalar = mu_s if mu_h else None       # homogeneous mu: V = P^-1 W Kz from the rank-N structure of P (trx_hmodes)
+        if swept:
+            self._keep_swept_modes()
+            return
         if diff:
             self._solve_layer_smatrix_diff()
         else:
@@ -447,6 +480,18 @@ class BatchedRCWA(FluxMixin, VolumeMixin):
         differentiable layer on, layers stay stored and solve_global_smatrix continues the cascade from the folded prefix over them
         (a global early return here used to leave such layers out of the cascade altogether)."""
         i = self.layer_N - 1
+        sw = self._swept
+        if sw is not None and i > sw["index"]:
+            # right of the swept layer: the same streaming cascade into a product of its own
+            if self.fold_layers and self._n_right_folded == i - sw["index"] - 1:
+                S = self._layer_S(i)
+                self._right_running = S if self._right_running is None else self._star(self._right_running, S, [[], []], [[], []])[0]
+                self.layer_S11[i] = self.layer_S21[i] = None
+                self.eps_conv[i] = None
+                self.eps_conv_x[i] = self.eps_conv_y[i] = None
+                self.eps_conv_xx[i] = self.eps_conv_xy[i] = self.eps_conv_yy[i] = None
+                self._n_right_folded += 1
+            return
         if not self.fold_layers or getattr(self, "_diff", False) or self._n_folded != i:
             return
         S = self._layer_S(i)
@@ -459,6 +504,94 @@ class BatchedRCWA(FluxMixin, VolumeMixin):
         self.eps_conv_x[i] = self.eps_conv_y[i] = None
         self.eps_conv_xx[i] = self.eps_conv_xy[i] = self.eps_conv_yy[i] = None
         self._n_folded = i + 1
+
+    def _keep_swept_modes(self):
+        """The swept layer: V = P^-1 W Kz (rcwa.py:1248, 1264; trx_hmodes for a homogeneous mu) next to W and kz; no layer S-matrix."""
+        eng = self.engine
+        W, kz = self.E_eigvec[-1], self.kz_norm[-1]
+        if self._mu_scalar is not None:
+            V = eng.hmodes(self.eps_conv[-1], self._mu_scalar, self.Kx_norm_dn, self.Ky_norm_dn, W, kz)
+        else:
+            V = eng.solve(self.P[-1], W * kz[:, None, :])
+        self.H_eigvec.append(V)
+        for lst in (self.layer_S11, self.layer_S21, self.Cplus, self.Cminus):
+            lst.append(None)
+        if self.fold_layers:              # as a folded layer: the matrices the modes came from are not read again
+            i = self.layer_N - 1
+            self.eps_conv[i] = self.P[i] = self.Q[i] = None
+            self.eps_conv_x[i] = self.eps_conv_y[i] = None
+            self.eps_conv_xx[i] = self.eps_conv_xy[i] = self.eps_conv_yy[i] = None
+
+    def _swept_sides(self):
+        """(Lft, Rgt): everything left / right of the swept layer as one S-matrix each -- None (nothing there), a list of four BlockDiag2
+        (half-space and homogeneous layers only) or of four [B,n,n] tensors."""
+        i = self._swept["index"]
+        none = [[], []]
+        Lft = None
+        first = 0
+        if self._n_folded > 0:
+            Lft, first = self._running, self._n_folded
+        for j in range(first, i):
+            Lft = self._layer_S(j) if Lft is None else self._star(Lft, self._layer_S(j), none, none)[0]
+        if self.has_in:
+            Lft = self._Sin if Lft is None else self._star(self._Sin, Lft, none, none)[0]
+        Rgt = None
+        first = i + 1
+        if self._n_right_folded > 0:
+            Rgt, first = self._right_running, i + 1 + self._n_right_folded
+        for j in range(first, self.layer_N):
+            Rgt = self._layer_S(j) if Rgt is None else self._star(Rgt, self._layer_S(j), none, none)[0]
+        if self.has_out:
+            Rgt = self._Sout if Rgt is None else self._star(Rgt, self._Sout, none, none)[0]
+        return Lft, Rgt
+
+    def _solve_swept(self, orders, direction, port, polarization, ref_order, power_norm, evanscent):
+        """solve_S_parameters of a solver with a swept layer: [B, T, len(orders)]."""
+        orders, polarization, oi, ri, k = self._sparam_args(orders, direction, port, polarization, ref_order)
+        cols = self._sparam_columns(ri, polarization)
+        sw = self._swept
+        i = sw["index"]
+        ops = []
+        for S in self._swept_sides():
+            if S is not None and self._is_bd(S):
+                S = torch.stack([torch.stack(blk.d, dim=0) for blk in S], dim=0).to(self._cdtype).contiguous()          # [4,4,B,N]
+            ops.append(S)
+        vfinv = torch.stack(self._Vfinv.d, dim=0).to(self._cdtype).contiguous()                                         # [4,B,N]
+        prep = self.engine.thickness_prepare(self.E_eigvec[i], self.H_eigvec[i], vfinv, ops[0], ops[1], 0 if k < 2 else 1, cols)
+        phase = torch.exp(1j * (self.omega[:, None] * sw["d"])[:, :, None] * self.kz_norm[i][:, None, :])               # [B, T, n]   rcwa.py:1246
+        chunk = self.thickness_chunk
+        if not chunk:
+            from .sweep import auto_thickness_chunk
+            chunk = auto_thickness_chunk(self.B, sw["d"].shape[1], self.n, len(cols), self._cdtype, self._device)
+        out = self.engine.thickness_columns(prep, phase, 0 if k in (0, 3) else 1, chunk=chunk)                          # [B, T, n, m]
+        vals = [self._sparam_values(lambda c, t=t: out[:, t, :, cols.index(c)], k, oi, ri, polarization, power_norm, evanscent)
+                for t in range(out.shape[1])]
+        return torch.stack(vals, dim=1)
+
+    def _refuse_swept(self, what):
+        if self._swept is not None:
+            raise ValueError(f"{what} is not available on a solver with a swept layer (add_layer(..., swept=True)): there is no single stack to "
+                             "solve; solve_S_parameters(...) returns the S-parameters of every thickness")
+
+    def power_flux(self, *a, **kw):
+        self._refuse_swept("power_flux")
+        return super().power_flux(*a, **kw)
+
+    def incident_flux(self, *a, **kw):
+        self._refuse_swept("incident_flux")
+        return super().incident_flux(*a, **kw)
+
+    def absorption(self, *a, **kw):
+        self._refuse_swept("absorption")
+        return super().absorption(*a, **kw)
+
+    def volume_integral(self, *a, **kw):
+        self._refuse_swept("volume_integral")
+        return super().volume_integral(*a, **kw)
+
+    def absorption_by_region(self, *a, **kw):
+        self._refuse_swept("absorption_by_region")
+        return super().absorption_by_region(*a, **kw)
 
     def _add_homogeneous_layer_bd(self, thickness, eps_s, mu_s):
         """Homogeneous layer without field bookkeeping (keep_coupling=False): every operator of rcwa.py:1206-1222 and 1244-1281
@@ -781,6 +914,7 @@ class BatchedRCWA(FluxMixin, VolumeMixin):
         return S, C, None
 
     def solve_global_smatrix(self):                                                     # rcwa.py:173-211
+        self._refuse_swept("solve_global_smatrix")
         S, C, _ = self._cascade()
         if self._is_bd(S):                                                              # only homogeneous media: densify for the read-out
             S = [blk.dense().to(self._cdtype) for blk in S]
@@ -794,7 +928,10 @@ class BatchedRCWA(FluxMixin, VolumeMixin):
         path (keep_coupling=False, no differentiable layer, a dense S before it), only the one or two columns of the one block that the
         read-out takes are computed (Engine.redheffer_halfspace_columns: one LU instead of the 4.33 n^3 product), and `self.S` / `self.C` are
         NOT set (they keep whatever an earlier solve_global_smatrix left).  Every other case -- keep_coupling, a differentiable stack, no
-        half-space, only homogeneous layers -- runs solve_global_smatrix() and reads out of self.S as S_parameters does."""
+        half-space, only homogeneous layers -- runs solve_global_smatrix() and reads out of self.S as S_parameters does.
+        On a solver with a swept layer (add_layer(..., swept=True)) the result is [B, T, len(orders)], one row per thickness."""
+        if self._swept is not None:
+            return self._solve_swept(orders, direction, port, polarization, ref_order, power_norm, evanscent)
         orders, polarization, oi, ri, k = self._sparam_args(orders, direction, port, polarization, ref_order)
         S, C, side = self._cascade(defer_last=True)
         if side is None:

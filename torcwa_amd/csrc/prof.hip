@@ -114,6 +114,7 @@ extern "C" const char* trx_prof_tag_name(int tag) {
                                             "qr_window_kernel", "hess_gemv_kernel", "hess_col_kernel", "lu_panel_kernel", "apply_links_kernel<0>",
                                             "gemm<N,N> fp32", "gemm<other ops> fp32",
                                             "phase:balance", "phase:hessenberg", "phase:qr", "phase:schur_vectors", "phase:refinement",
-                                            "sym_fold", "sym_unfold"};
+                                            "sym_fold", "sym_unfold",
+                                            "thickness_prepare", "thickness_columns:K_gemm", "thickness_columns:lu_solve", "thickness_columns:readout"};
     return (tag >= 0 && tag < PROF_NTAGS) ? names[tag] : "?";
 }

@@ -10,7 +10,10 @@ enum ProfTag { PROF_GEMM_NN = 0, PROF_GEMM_OTHER = 1, PROF_QR_PREPARE = 2, PROF_
                // wall-clock PHASES of trx_eig (one event pair per call on the caller's stream; the QR phase from fork to join of its iteration groups)
                PROF_PH_BALANCE = 11, PROF_PH_HESSENBERG = 12, PROF_PH_QR = 13, PROF_PH_VECTORS = 14, PROF_PH_REFINE = 15,
                // mirror-symmetry folding (symfold.hip): both passes of trx_sym_fold, and trx_sym_unfold with its zero fill
-               PROF_SYM_FOLD = 16, PROF_SYM_UNFOLD = 17, PROF_NTAGS = 18 };
+               PROF_SYM_FOLD = 16, PROF_SYM_UNFOLD = 17,
+               // thickness sweeps (thickness.hip): one event pair per call around trx_thickness_prepare, and around the three stages of
+               // trx_thickness_columns (K assembly and its GEMMs; LU of K and the solve; amplitudes and read-out)
+               PROF_THICK_PREPARE = 18, PROF_THICK_KGEMM = 19, PROF_THICK_LU = 20, PROF_THICK_READOUT = 21, PROF_NTAGS = 22 };
 // (PROF_GEMM_*_F32: the fp32 GEMMs -- first stage of the mixed-precision eigensolver, precision="native" -- are counted apart from the fp64 ones:
 // other peak, other roofline)
 

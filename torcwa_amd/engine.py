@@ -619,6 +619,89 @@ class Engine:
                                               nws, self.stream))
         return out
 
+    # -- thickness sweeps that reuse a layer's modes -----------------------------------------------------
+    def _tk_operand(self, op, dt, B, n):
+        """One side of a swept layer for the C ABI: None (nothing there: the identity), a [4,4,B,N] tensor of diagonals (block-diagonal S-matrix,
+        as redheffer_halfspace takes it) or a list of four [B,n,n] tensors.  Returns (kind, pointer, objects to keep alive)."""
+        if op is None:
+            return 0, None, None
+        if torch.is_tensor(op):
+            bd = self._c(op.to(dt))
+            if tuple(bd.shape) != (4, 4, B, n // 2):
+                raise ValueError(f"thickness sweep: a block-diagonal operand must be [4, 4, {B}, {n // 2}], got {list(bd.shape)}")
+            self._check(bd)
+            return 1, bd.data_ptr(), bd
+        S = [self._c(t) for t in op]
+        self._check(*S)
+        if len(S) != 4 or any(tuple(t.shape) != (B, n, n) or t.dtype != dt for t in S):
+            raise ValueError(f"thickness sweep: a dense operand is four [{B}, {n}, {n}] tensors of dtype {dt}")
+        arr = (ctypes.c_void_p * 4)(*[t.data_ptr() for t in S])
+        return 2, ctypes.addressof(arr), (S, arr)
+
+    @_phase("thickness sweep: prepare (trx_thickness_prepare)")
+    def thickness_prepare(self, W, V, vfinv, left, right, direction, cols):
+        """The thickness-independent part of a thickness sweep of one layer (include/trx.h: trx_thickness_prepare).  W, V [B,n,n]: the layer's
+        modes; vfinv [4,B,N]; left / right: everything on that side of the layer as one S-matrix (see _tk_operand); direction 0 = forward,
+        1 = backward incidence; cols: 1 to 16 column indices in [0, n).  Returns the handle Engine.thickness_columns takes."""
+        W, V, vfinv = self._c(W), self._c(V), self._c(vfinv)
+        self._check(W, V, vfinv)
+        B, n, _ = W.shape
+        N = n // 2
+        dt = W.dtype
+        cols = [int(c) for c in cols]
+        m = len(cols)
+        if int(direction) not in (0, 1):
+            raise ValueError(f"thickness_prepare: direction must be 0 (forward) or 1 (backward), got {direction!r}")
+        lk, lp, lkeep = self._tk_operand(left, dt, B, n)
+        rk, rp, rkeep = self._tk_operand(right, dt, B, n)
+        rho = torch.empty((2, B, n, n), dtype=dt, device=self.device)
+        src = torch.empty((2, B, n, max(m, 1)), dtype=dt, device=self.device)
+        AB = torch.empty((2, B, n, n), dtype=dt, device=self.device)
+        piv, info = self._ints(B * n), self._ints(2 * B)
+        nws = self.lib.thickness_prepare_ws_bytes(_CODE[dt], N, B)
+        ws = self._ws(nws)
+        pc = (ctypes.c_int * max(m, 1))(*cols)
+        self.lib.check(self.lib.thickness_prepare(_CODE[dt], W.data_ptr(), V.data_ptr(), vfinv.data_ptr(), lk, lp, rk, rp, int(direction),
+                                                  ctypes.addressof(pc), m, N, B, rho[0].data_ptr(), rho[1].data_ptr(), src.data_ptr(), AB.data_ptr(),
+                                                  piv.data_ptr(), info.data_ptr(), ws.data_ptr(), nws, self.stream))
+        self._info(info, "thickness_prepare")
+        return dict(rho=rho, src=src, AB=AB, direction=int(direction), m=m, B=B, N=N, dtype=dt, left=(lk, lp, lkeep), right=(rk, rp, rkeep))
+
+    @_phase("thickness sweep: columns (trx_thickness_columns)")
+    def thickness_columns(self, prep, phase, port, chunk=None):
+        """[B, T, n, m]: for every thickness the columns (those of the prepare call) of the block of the whole stack's S-matrix that
+        (direction, port) reads (include/trx.h: trx_thickness_columns).  phase [B, T, n] = exp(i omega kz d_t); port 0 = transmission,
+        1 = reflection; chunk: thicknesses per library call (the workspace holds two n x n matrices per point and thickness; default: all T)."""
+        B, N, m, dt = prep["B"], prep["N"], prep["m"], prep["dtype"]
+        n = 2 * N
+        phase = self._c(phase)
+        self._check(prep["rho"], phase)
+        if phase.dim() != 3 or phase.shape[0] != B or phase.shape[2] != n:
+            raise ValueError(f"thickness_columns: phase must be [{B}, T, {n}], got {list(phase.shape)}")
+        if int(port) not in (0, 1):
+            raise ValueError(f"thickness_columns: port must be 0 (transmission) or 1 (reflection), got {port!r}")
+        T = phase.shape[1]
+        out = torch.empty((B, T, n, m), dtype=dt, device=self.device)
+        info = self._ints(B * T)
+        chunk = T if not chunk else max(1, min(int(chunk), T))
+        if B > 0:
+            chunk = max(1, min(chunk, 65535 // B))
+        esz = phase.element_size()
+        (lk, lp, _), (rk, rp, _) = prep["left"], prep["right"]
+        rho, src, AB = prep["rho"], prep["src"], prep["AB"]
+        for t0 in range(0, T, chunk):
+            Tc = min(chunk, T - t0)
+            nws = self.lib.thickness_columns_ws_bytes(_CODE[dt], N, B, Tc, m)
+            ws = self._ws(nws)
+            piv = self._ints(B * Tc * (n + 1))
+            self.lib.check(self.lib.thickness_columns(_CODE[dt], rho[0].data_ptr(), rho[1].data_ptr(), src.data_ptr(), AB.data_ptr(),
+                                                      phase.data_ptr() + t0 * n * esz, T, Tc, prep["direction"], int(port), lk, lp, rk, rp, m, N, B,
+                                                      out.data_ptr() + t0 * n * m * esz, piv.data_ptr(), info.data_ptr() + 4 * t0, ws.data_ptr(), nws,
+                                                      self.stream))
+            del ws, piv
+        self._info(info, "thickness_columns")
+        return out
+
     # -- mirror-symmetry folding ------------------------------------------------------------------------
     @_phase("symmetry fold (trx_sym_fold)")
     def sym_fold(self, A, plan):

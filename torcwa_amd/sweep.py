@@ -116,6 +116,12 @@ _LI_EXTRA = 0.5
 # inverse's workspace and the three product matrices: five more N x N) -- 8 N^2 = 2 n^2
 _NV_EXTRA = 2.0
 _HEADROOM = 0.10                               # fraction of the device memory a sweep leaves free
+# Thickness sweep (add_layer(..., swept=True)), matrices per (point, thickness) that one trx_thickness_columns call holds, from its workspace
+# layout (include/trx.h): X rho X and K, 2 n x n; the amplitudes and the pivots are O(n m) and O(n) next to them.  They come on top of what stays
+# per point after the eigendecomposition -- W, V, rho_L, rho_R, A, B and the prepare workspace (7) and up to two dense sides (8) -- which is
+# below the eigensolver's peak that _POINT_MATRICES already covers.  Not measured on the allocator yet: auto_thickness_chunk() asks for what is free
+# at the time of the call, with the same headroom.
+_THICKNESS_MATRICES = 2.0
 
 
 # absorption=True (keep_coupling=True, no streaming cascade), matrices per point and layer on top of _POINT_MATRICES.  Derived from the code: every
@@ -154,6 +160,22 @@ def auto_chunk(B, order, n_layers, precision, device, dtype=torch.complex64, str
     if fit >= B:
         return B
     return fit if fit < 8 else fit - fit % 8
+
+
+def auto_thickness_chunk(B, T, n, m, cdtype, device):
+    """Thicknesses per trx_thickness_columns call that fit the free HBM of `device` next to B resident points (_THICKNESS_MATRICES), with
+    _HEADROOM to spare; T when everything fits.  Raises with the numbers when not even one thickness fits."""
+    if device.type != "cuda":
+        return T
+    elem = 16 if cdtype == torch.complex128 else 8
+    per = B * ((_THICKNESS_MATRICES * n * n + 5 * n * m) * elem + 4 * (n + 1))
+    free, total = torch.cuda.mem_get_info(device)
+    free += torch.cuda.memory_reserved(device) - torch.cuda.memory_allocated(device)
+    fit = int((free - _HEADROOM * total) // per)
+    if fit < 1:
+        raise RuntimeError("torcwa_amd thickness sweep: one thickness of %d points needs about %.1f GB of HBM (%d x %d complex matrices x %.0f per "
+                           "point), but only %.1f GB are free on %s; lower the chunk of points" % (B, per / 1e9, n, n, _THICKNESS_MATRICES, free / 1e9, device))
+    return min(int(T), fit)
 
 
 def _slice(v, lo, hi, B):
@@ -282,3 +304,62 @@ def solve_single_layer_sweep(freq, eps_grids, thickness, order, L, **kw):
               grids off a reserved set of compute units: profiles/r06_ab/cumask.txt).
     """
     return solve_stack_sweep(freq.to(eps_grids.device), [(thickness, eps_grids)], order, L, **kw)
+
+
+def solve_thickness_sweep(freq, layers, order, L, *, layer=0, thicknesses, eps_in=None, eps_out=None, inc_ang=0.0, azi_ang=0.0,
+                          dtype=torch.complex64, precision="high", engine=None, chunk=None, streams=1, orders=((0, 0),), polarization="xx",
+                          direction="forward", port="transmission", check_info=True, eig_route="auto", fourier_rule="laurent",
+                          nv_sigma=NV_SIGMA_DEFAULT, symmetry=None, symmetry_tol=1e-6, thickness_chunk=None):
+    """B sweep points x T thicknesses of ONE layer of a stack: the modes of `layers[layer]` are computed once per point and every thickness
+    costs one GEMM and one LU (BatchedRCWA.add_layer(..., swept=True)) instead of a new eigendecomposition.  Returns [B, T, len(orders)].
+
+    layers as in solve_stack_sweep; the thickness entry of layers[layer] is ignored and may be None.  thicknesses: [T] (shared by the points)
+    or [B, T].  Keywords as solve_stack_sweep, without absorption / source (a swept solve keeps no coupling matrices).  chunk: points solved in
+    lock-step (default: auto_chunk); thickness_chunk: thicknesses per library call (default: what the free HBM holds, `auto_thickness_chunk`)."""
+    from .engine import default_engine
+    check_fourier_rule(fourier_rule)
+    B = freq.shape[0]
+    layer = int(layer)
+    if not (-len(layers) <= layer < len(layers)):
+        raise ValueError(f"layer must index one of the {len(layers)} layers, got {layer}")
+    layer %= len(layers)
+    d = torch.as_tensor(thicknesses)
+    if d.dim() == 1:
+        per_point = False
+    elif d.dim() == 2 and d.shape[0] == B:
+        per_point = True
+    else:
+        raise ValueError(f"thicknesses must be [T] or [{B}, T], got {list(d.shape)}")
+    eng = engine if engine is not None else default_engine()
+    old_check, eng.check_info = eng.check_info, check_info
+    chunk = auto_chunk(B, order, len(layers), precision, freq.device, dtype=dtype, streams=streams, fourier_rule=fourier_rule) if not chunk else int(chunk)
+    if streams > 1 and chunk >= B:
+        chunk = -(-B // streams)
+    spans = [(lo, min(B, lo + chunk)) for lo in range(0, B, chunk)]
+    outs = [None] * len(spans)
+    route_hint = {}
+
+    def run(i):
+        lo, hi = spans[i]
+        sim = BatchedRCWA(freq[lo:hi], order, L, dtype=dtype, precision=precision, engine=engine, keep_coupling=False, fold_layers=True,
+                          eig_route=eig_route, route_hint=route_hint, fourier_rule=fourier_rule, nv_sigma=nv_sigma, symmetry=symmetry,
+                          symmetry_tol=symmetry_tol)
+        sim.thickness_chunk = thickness_chunk
+        if eps_in is not None:
+            sim.add_input_layer(eps=_slice(eps_in, lo, hi, B))
+        if eps_out is not None:
+            sim.add_output_layer(eps=_slice(eps_out, lo, hi, B))
+        sim.set_incident_angle(_slice(inc_ang, lo, hi, B), _slice(azi_ang, lo, hi, B))
+        for j, lay in enumerate(layers):
+            lay = tuple(_slice(v, lo, hi, B) for v in lay)
+            if j == layer:
+                sim.add_layer(d[lo:hi] if per_point else d, *lay[1:], swept=True)
+            else:
+                sim.add_layer(*lay)
+        outs[i] = sim.solve_S_parameters([list(o) for o in orders], direction=direction, port=port, polarization=polarization)
+
+    try:
+        _run_spans(run, spans, streams, freq.device)
+    finally:
+        eng.check_info = old_check
+    return torch.cat(outs, dim=0)
