@@ -208,7 +208,8 @@ int trx_eig_backward(int dtype, const void* w, const void* V, const void* gw, co
 /* ---- layer eigenproblem assembly: torcwa/rcwa.py:1224-1232 (`_eigen_decomposition`, P and Q) -------------------
  * P = [[Kx Ei Ky, M - Kx Ei Kx],[Ky Ei Ky - M, -Ky Ei Kx]],  Q = [[-Kx Mi Ky, Kx Mi Kx - E],[E - Ky Mi Ky, Ky Mi Kx]]
  * E, Einv, Mu, Muinv: [batch,N,N] (Einv = inverse of the permittivity convolution matrix, etc.);
- * kx, ky: [batch,N] complex (the diagonals of Kx_norm, Ky_norm, rcwa.py:1138-1141); P, Q: [batch,2N,2N]. */
+ * kx, ky: [batch,N] complex (the diagonals of Kx_norm, Ky_norm, rcwa.py:1138-1141); P, Q: [batch,2N,2N].
+ * One implementation (csrc/assembly.hip) serves this entry, trx_build_pq_aniso and trx_build_pq_tensor, and likewise the three trx_build_a*. */
 int trx_build_pq(int dtype, const void* E, const void* Einv, const void* Mu, const void* Muinv, const void* kx,
                  const void* ky, int N, int batch, void* P, void* Q, void* stream);
 
@@ -285,7 +286,8 @@ int trx_build_a(int dtype, const void* E, const void* Einv, const void* mu, cons
 
 /* P, Q (as trx_build_pq) with a convolution matrix per field component (Li's rule; the full in-plane tensor: trx_build_pq_tensor):
  *   P = [[Kx Ei Ky, My - Kx Ei Kx],[Ky Ei Ky - Mx, -Ky Ei Kx]],  Q = [[-Kx Mi Ky, Kx Mi Kx - Ey],[Ex - Ky Mi Ky, Ky Mi Kx]]
- * Einv / Minv: inverses of the LAURENT matrices (they act on Ez / Hz).  Ex = Ey = E, Mx = My = M gives trx_build_pq. */
+ * Einv / Minv: inverses of the LAURENT matrices (they act on Ez / Hz).  Ex = Ey = E, Mx = My = M gives trx_build_pq
+ * (the same code: bit-identical results). */
 int trx_build_pq_aniso(int dtype, const void* Ex, const void* Ey, const void* Einv, const void* Mx, const void* My, const void* Minv,
                        const void* kx, const void* ky, int N, int batch, void* P, void* Q, void* stream);
 /* A = P Q for homogeneous mu[batch] with per-component Ex, Ey (two N^3 GEMMs, as trx_build_a):
@@ -296,7 +298,8 @@ int trx_build_a_aniso(int dtype, const void* Ex, const void* Ey, const void* Ein
 
 /* P, Q (as trx_build_pq) with the in-plane permittivity tensor of trx_convmat_nv (Eyx = Exy):
  *   P = [[Kx Ei Ky, M - Kx Ei Kx],[Ky Ei Ky - M, -Ky Ei Kx]],  Q = [[-Kx Mi Ky - Exy, Kx Mi Kx - Eyy],[Exx - Ky Mi Ky, Ky Mi Kx + Exy]]
- * Einv: inverse of the LAURENT [eps] (it acts on Ez); Mu / Muinv as trx_build_pq.  Exx = Eyy = E, Exy = 0 gives trx_build_pq. */
+ * Einv: inverse of the LAURENT [eps] (it acts on Ez); Mu / Muinv as trx_build_pq.  Exx = Eyy = E, Exy = 0 gives trx_build_pq (the same
+ * code with the Exy terms added: equal results). */
 int trx_build_pq_tensor(int dtype, const void* Exx, const void* Exy, const void* Eyy, const void* Einv, const void* Mu, const void* Muinv,
                         const void* kx, const void* ky, int N, int batch, void* P, void* Q, void* stream);
 /* A = P Q for homogeneous mu[batch] with the tensor (one N x 2N GEMM, the cost of trx_build_a_aniso's two N^3 products):

@@ -200,13 +200,13 @@ def test_build_pq_a_aniso(backend):
         I = torch.eye(N, dtype=torch.complex128)
         Pr, Qr = pq_ref(Ex[b], Ey[b], E[b], mu[b] * I, mu[b] * I, mu[b] * I, kx[b], ky[b])
         assert _rel(A[b], Pr @ Qr) < 1e-12
-    # Ex = Ey = E, Mx = My = M: the Laurent entry points
+    # Ex = Ey = E, Mx = My = M: the Laurent entry points (one implementation behind both: identical results)
     P0, Q0 = eng.build_pq(d(E), d(Ei), d(M), d(Mi), d(kx), d(ky))
     P1, Q1 = eng.build_pq_aniso(d(E), d(E), d(Ei), d(M), d(M), d(Mi), d(kx), d(ky))
-    assert _rel(P1.cpu(), P0.cpu()) < 1e-13 and _rel(Q1.cpu(), Q0.cpu()) < 1e-13
+    assert torch.equal(P1.cpu(), P0.cpu()) and torch.equal(Q1.cpu(), Q0.cpu())
     A0 = eng.build_a(d(E), d(Ei), d(mu), d(kx), d(ky)).cpu()
     A1 = eng.build_a_aniso(d(E), d(E), d(Ei), d(mu), d(kx), d(ky)).cpu()
-    assert _rel(A1, A0) < 1e-13
+    assert torch.equal(A1, A0)
 
 
 # ---- 4. full path against the oracle with Li's matrices in Q (and P for a patterned mu) -----------------------------------------------------

@@ -1,5 +1,6 @@
 """The middle of the pipeline at block level: trx_layer_smatrix (with the right solves of lu.hip behind it), trx_redheffer and the XY
-coupling factors, trx_eig_backward, trx_build_pq and trx_build_a, each against an independent numpy restatement of the same operation.
+coupling factors, trx_eig_backward and the six trx_build_pq* / trx_build_a* entries, each against an independent numpy restatement of the
+same operation.
 
 Policy ("Block tests"):
   * independent algebra: the layer reference inverts the 2n x 2n matrix of torcwa/rcwa.py:1268-1274 (the kernel: two n x n solves), the star
@@ -415,55 +416,85 @@ def test_eig_backward(backend, dtype, n, batch, case):
     print(f"eig_backward worst err/max(e_plain, n eps) = {max(ratios):.3f}")
 
 
-# ---- 4. trx_build_pq, trx_build_a -----------------------------------------------------------------------------------------------------
+# ---- 4. trx_build_pq*, trx_build_a*: the one assembly implementation through the entries of the three Fourier rules ------------------------
 
-def _pq_dense(E, Ei, M, Mi, kx, ky):
-    """include/trx.h: P = [[Kx Ei Ky, M - Kx Ei Kx],[Ky Ei Ky - M, -Ky Ei Kx]],  Q = [[-Kx Mi Ky, Kx Mi Kx - E],[E - Ky Mi Ky, Ky Mi Kx]]."""
+RULES = ["laurent", "li", "normal"]
+_SUFFIX = {"laurent": "", "li": "_aniso", "normal": "_tensor"}
+
+
+def _pq_dense(Exx, Exy, Eyy, Ei, Mx, My, Mi, kx, ky):
+    """include/trx.h, trx_build_pq_aniso and trx_build_pq_tensor in one:
+    P = [[Kx Ei Ky, My - Kx Ei Kx],[Ky Ei Ky - Mx, -Ky Ei Kx]],  Q = [[-Kx Mi Ky - Exy, Kx Mi Kx - Eyy],[Exx - Ky Mi Ky, Ky Mi Kx + Exy]]."""
     Kx, Ky = np.diag(kx), np.diag(ky)
-    P = np.block([[Kx @ Ei @ Ky, M - Kx @ Ei @ Kx], [Ky @ Ei @ Ky - M, -Ky @ Ei @ Kx]])
-    Q = np.block([[-Kx @ Mi @ Ky, Kx @ Mi @ Kx - E], [E - Ky @ Mi @ Ky, Ky @ Mi @ Kx]])
+    P = np.block([[Kx @ Ei @ Ky, My - Kx @ Ei @ Kx], [Ky @ Ei @ Ky - Mx, -Ky @ Ei @ Kx]])
+    Q = np.block([[-Kx @ Mi @ Ky - Exy, Kx @ Mi @ Kx - Eyy], [Exx - Ky @ Mi @ Ky, Ky @ Mi @ Kx + Exy]])
     return P, Q
+
+
+def _rule_tensor(rule, eps):
+    """(Exx, Exy, Eyy) that the entry of `rule` stands for, from its own permittivity arguments `eps` (include/trx.h): trx_build_pq / _a take
+    E (Exx = Eyy = E, Exy = 0), the _aniso entries Ex, Ey (Exy = 0), the _tensor entries Exx, Exy, Eyy."""
+    if rule == "laurent":
+        return eps[0], np.zeros_like(eps[0]), eps[0]
+    if rule == "li":
+        return eps[0], np.zeros_like(eps[0]), eps[1]
+    return eps
 
 
 @pytest.mark.parametrize("backend", BACKENDS)
 @pytest.mark.parametrize("dtype,tol", [(np.complex128, 1e-13), (np.complex64, 2e-5)])
 @pytest.mark.parametrize("N", [37, 300])
-def test_build_pq_dense_formula(backend, dtype, tol, N):
-    """trx_build_pq against np.block of the dense products (general, unrelated E, Einv, Mu, Muinv: the kernel must not assume they are
-    inverses of each other).  N = 300: the second column block of the assembly kernel.  Tolerances of test_gemm."""
+@pytest.mark.parametrize("rule", RULES)
+def test_build_pq_dense_formula(backend, dtype, tol, N, rule):
+    """trx_build_pq / _aniso / _tensor against np.block of the dense products (general, unrelated matrices: E, Einv, Mu, Muinv, and per rule
+    Ex, Ey, Mx, My or Exx, Exy, Eyy -- the kernel must not assume that any two are equal or inverses of each other).  N = 300: the second
+    column block of the assembly kernel.  Tolerances of test_gemm."""
     be = get_backend(backend)
     batch, n = 2, 2 * N
-    rng = np.random.default_rng([20264, N])
-    E, Ei, M, Mi = [crandn(rng, (batch, N, N)).astype(dtype) for _ in range(4)]
+    rng = np.random.default_rng([20264, N] + ([RULES.index(rule)] if rule != "laurent" else []))
+    draw = lambda: crandn(rng, (batch, N, N)).astype(dtype)
+    eps = [draw() for _ in range({"laurent": 1, "li": 2, "normal": 3}[rule])]
+    Ei = draw()
+    mus = [draw() for _ in range(2 if rule == "li" else 1)]           # M, or Li's Mx, My
+    Mi = draw()
     kx, ky = crandn(rng, (batch, N)).astype(dtype), crandn(rng, (batch, N)).astype(dtype)
-    dev = [be.dev(a) for a in (E, Ei, M, Mi, kx, ky)]
+    dev = [be.dev(a) for a in (*eps, Ei, *mus, Mi, kx, ky)]
     P, Q = Guarded(be, batch * n * n, dtype), Guarded(be, batch * n * n, dtype)
-    rc = be.lib.build_pq(dtcode(dtype), *[be.ptr(d) for d in dev], N, batch, P.ptr(), Q.ptr(), be.stream)
+    rc = getattr(be.lib, "build_pq" + _SUFFIX[rule])(dtcode(dtype), *[be.ptr(d) for d in dev], N, batch, P.ptr(), Q.ptr(), be.stream)
     assert rc == 0
     hP, hQ = P.host((batch, n, n)), Q.host((batch, n, n))
     for b in range(batch):
-        rP, rQ = _pq_dense(*[a[b].astype(np.complex128) for a in (E, Ei, M, Mi, kx, ky)])
+        rP, rQ = _pq_dense(*[a[b].astype(np.complex128) for a in (*_rule_tensor(rule, eps), Ei, mus[0], mus[-1], Mi, kx, ky)])
         assert relmax(hP[b], rP) < tol and relmax(hQ[b], rQ) < tol, (relmax(hP[b], rP), relmax(hQ[b], rQ))
 
 
 @pytest.mark.parametrize("backend", BACKENDS)
 @pytest.mark.parametrize("dtype,tol", [(np.complex128, 1e-13), (np.complex64, 2e-5)])
 @pytest.mark.parametrize("N", [37, 300])
-def test_build_a_is_p_times_q(backend, dtype, tol, N):
-    """trx_build_a (two N^3 products from the block structure) against the dense A = P Q with Mu = mu I, two different mu in the batch.  The
-    2N-deep product of the complex128 case is formed in clongdouble.  Tolerances of test_gemm."""
+@pytest.mark.parametrize("rule", RULES)
+def test_build_a_is_p_times_q(backend, dtype, tol, N, rule):
+    """trx_build_a / _aniso / _tensor (N^3-sized products from the block structure) against the dense A = P Q with Mu = mu I, two different mu
+    in the batch.  Laurent's Einv is the inverse of E as before; Li's Ex, Ey and the tensor Exx, Exy, Eyy are unrelated to the matrix Einv
+    inverts.  The 2N-deep product of the complex128 case is formed in clongdouble.  Tolerances of test_gemm."""
     be = get_backend(backend)
     batch, n = 2, 2 * N
-    rng = np.random.default_rng([20265, N])
-    E = (crandn(rng, (batch, N, N)) * (0.5 / np.sqrt(N)) + 3.0 * np.eye(N)).astype(dtype)
+    rng = np.random.default_rng([20265, N] + ([RULES.index(rule)] if rule != "laurent" else []))
+    diag_dominant = lambda: (crandn(rng, (batch, N, N)) * (0.5 / np.sqrt(N)) + 3.0 * np.eye(N)).astype(dtype)
+    E = diag_dominant()
     Ei = np.linalg.inv(E.astype(np.complex128)).astype(dtype)
+    if rule == "laurent":
+        eps = [E]
+    elif rule == "li":
+        eps = [diag_dominant(), diag_dominant()]
+    else:
+        eps = [diag_dominant(), (crandn(rng, (batch, N, N)) * (0.5 / np.sqrt(N))).astype(dtype), diag_dominant()]
     mu = np.array([1.0 + 0.0j, 1.3 - 0.2j]).astype(dtype)
     kx, ky = crandn(rng, (batch, N)).astype(dtype), crandn(rng, (batch, N)).astype(dtype)
-    dev = [be.dev(a) for a in (E, Ei, mu, kx, ky)]
+    dev = [be.dev(a) for a in (*eps, Ei, mu, kx, ky)]
     A = Guarded(be, batch * n * n, dtype)
-    nws = be.lib.build_a_ws_bytes(dtcode(dtype), N, batch)
+    nws = getattr(be.lib, "build_a" + _SUFFIX[rule] + "_ws_bytes")(dtcode(dtype), N, batch)
     ws = Guarded(be, nws, np.uint8)
-    rc = be.lib.build_a(dtcode(dtype), *[be.ptr(d) for d in dev], N, batch, A.ptr(), ws.ptr(), nws, be.stream)
+    rc = getattr(be.lib, "build_a" + _SUFFIX[rule])(dtcode(dtype), *[be.ptr(d) for d in dev], N, batch, A.ptr(), ws.ptr(), nws, be.stream)
     assert rc == 0
     ws.host()
     hA = A.host((batch, n, n))
@@ -471,7 +502,8 @@ def test_build_a_is_p_times_q(backend, dtype, tol, N):
     for b in range(batch):
         m = mu[b].astype(np.complex128)
         I = np.eye(N)
-        rP, rQ = _pq_dense(E[b].astype(np.complex128), Ei[b].astype(np.complex128), m * I, I / m, kx[b].astype(np.complex128), ky[b].astype(np.complex128))
+        rP, rQ = _pq_dense(*[a[b].astype(np.complex128) for a in (*_rule_tensor(rule, eps), Ei)], m * I, m * I, I / m,
+                           kx[b].astype(np.complex128), ky[b].astype(np.complex128))
         ref = (rP.astype(wd) @ rQ.astype(wd)).astype(np.complex128)
         assert relmax(hA[b], ref) < tol, relmax(hA[b], ref)
 

@@ -8,6 +8,7 @@ libtrx call (include/trx.h).  The drop-in class `torcwa_amd.rcwa` is the B=1 vie
 All per-point scalars (`freq`, angles, homogeneous eps/mu, thickness) may be python scalars or [B] tensors.
 """
 import warnings
+from collections import namedtuple
 
 import numpy as np
 import torch
@@ -32,6 +33,13 @@ FOURIER_RULES = ("laurent", "li", "normal")
 # fourier_rule="normal": default width (grid cells) of the Gaussian that smooths the structure tensor of a grid into the normal-vector field
 # (include/trx.h: trx_normal_field); chosen by the CPU study in profiles/normal_vector.txt
 NV_SIGMA_DEFAULT = 6.0
+
+
+# The factorised medium of one layer: Laurent's E, M and their inverses (None until needed; M = Minv = None for a lean layer, see
+# BatchedRCWA._factorise), the per-point scalars of a homogeneous eps / mu (else None), and the matrices that stand for eps and mu per field
+# component in P, Q and A (include/trx.h).  Laurent's rule: exx = eyy = E, mx = my = M, exy = None; Li's rule: its own exx, eyy (mx, my) for a
+# patterned eps (mu); the normal-vector rule: the tensor exx, exy, eyy.
+Medium = namedtuple("Medium", "E Einv M Minv eps_s mu_s exx exy eyy mx my")
 
 
 def check_fourier_rule(rule):
@@ -316,40 +324,126 @@ class BatchedRCWA(FluxMixin, VolumeMixin):
             if normal_field is not None:
                 raise ValueError("symmetry= cannot be combined with add_layer(normal_field=...): a caller-supplied field is not checked for the mirror; "
                                  "let the field be derived from the grid")
+        if eps_h and mu_h and not diff and not self.keep_coupling and not swept:
+            self._add_homogeneous_layer_bd(thickness, self._bvec(eps), self._bvec(mu))
+            self.symmetry_residual.append(None)
+            self._fold_last_layer()
+            return
+        fac, plan = self._factorise(eps, mu, eps_h, mu_h, normal_field, diff, eye)
+        keep = self.keep_coupling
+        eps_s, mu_s = fac.eps_s, fac.mu_s
+        self.eps_conv.append(fac.E)
+        self.mu_conv.append(fac.M)
+        self.eps_grid.append((self._bvec(eps) if eps_h else eps) if keep else None)
+        self.mu_grid.append((self._bvec(mu) if mu_h else mu) if keep else None)
+        keep_li = keep and fac.exy is None and fac.exx is not fac.E          # Li's Ex, Ey of a patterned eps
+        self.eps_conv_x.append(fac.exx if keep_li else None)
+        self.eps_conv_y.append(fac.eyy if keep_li else None)
+        keep_nv = keep and fac.exy is not None
+        self.eps_conv_xx.append(fac.exx if keep_nv else None)
+        self.eps_conv_xy.append(fac.exy if keep_nv else None)
+        self.eps_conv_yy.append(fac.eyy if keep_nv else None)
+        self.layer_N += 1
+        if swept:
+            d = torch.as_tensor(thickness, dtype=self._rdtype, device=self._device)
+            if d.dim() == 1:
+                d = d[None, :].expand(B, -1)
+            if d.dim() != 2 or d.shape[0] != B:
+                raise ValueError(f"add_layer(swept=True): thickness must be [T] or [{B}, T], got {list(d.shape)}")
+            self._swept = dict(index=self.layer_N - 1, d=d.contiguous())
+            self.thickness.append(None)          # no single thickness: see _swept["d"]
+        else:
+            d = self._bvec(thickness, self._rdtype)
+            self.thickness.append(d)
+        kxd, kyd = self.Kx_norm_dn, self.Ky_norm_dn
+        inv = (lambda A: ag.InverseFn.apply(A, eng)) if diff else eng.inverse
+        if fac.Einv is None:
+            fac = fac._replace(Einv=inv(fac.E))
+        if fac.Minv is None and fac.M is not None:
+            fac = fac._replace(Minv=inv(fac.M))
+        P, Q = self._pq(fac, diff)
+        if eps_h and mu_h:                                                              # rcwa.py:1206-1222
+            W = torch.eye(2 * N, dtype=cdt, device=self._device).expand(B, -1, -1).contiguous()
+            kz = torch.sqrt((eps_s * mu_s)[:, None] - kxd ** 2 - kyd ** 2)
+            kz = torch.where(torch.imag(kz) < 0, torch.conj(kz), kz)
+            kz = torch.cat((kz, kz), dim=1)
+        else:                                                                           # rcwa.py:1224-1242
+            if diff:
+                Eig.engine = eng
+                A = ag.GemmFn.apply(P, Q, eng)
+                # stable_eig_grad=False is the reference's plain torch.linalg.eig branch (rcwa.py:1238): its backward is never
+                # broadened.  The choice is bound to this graph node (not to the process-global at backward time).
+                lam, W = Eig.apply(A) if self.stable_eig_grad else Eig.apply(A, Eig.UNBROADENED)
+            else:
+                A = self._a(fac, P, Q)
+                # the factorised medium dies here, before the eigensolver's peak: E, M live on in eps_conv / mu_conv, Li's / the
+                # normal-vector matrices only in eps_conv_x / _y / _xx / _xy / _yy (keep_coupling)
+                del fac
+                # mixed-precision eigensolver: two Newton steps for a complex64 problem (1e-5 gate), three for complex128 (engine.eig)
+                steps = 3 if self._dtype == torch.complex128 else 2
+                if plan is None:
+                    lam, W = self._eig_call(A, refine_steps=steps)                          # torch_eig.py:14
+                else:
+                    lam, W, resid = self._eig_folded(A, plan, steps)
+                del A
+            kz = torch.sqrt(lam)
+            kz = torch.where(torch.imag(kz) < 0, -kz, kz)                               # rcwa.py:1241
+        self.symmetry_residual.append(resid if plan is not None else None)
+        self.P.append(P)
+        self.Q.append(Q)
+        self.kz_norm.append(kz)
+        self.E_eigvec.append(W)
+        self._mu_scalar = mu_s                         # homogeneous mu: V = P^-1 W Kz from the rank-N structure of P (trx_hmodes)
+        if swept:
+            self._keep_swept_modes()
+            return
+        if diff:
+            self._solve_layer_smatrix_diff()
+        else:
+            self._solve_layer_smatrix()
+        self._fold_last_layer()
+
+    def _grid(self, v):
+        """eps / mu grid [nx, ny] or [B, nx, ny] -> contiguous [B, nx, ny] on the device."""
+        g = torch.as_tensor(v, device=self._device)
+        if g.dim() == 2:
+            g = g[None].expand(self.B, -1, -1)
+        return g.contiguous()
+
+    def _factorise(self, eps, mu, eps_h, mu_h, normal_field, diff, eye):
+        """(Medium, plan): the convolution matrices of a layer under this solver's Fourier rule, and its symmetry folding plan (None without
+        symmetry=; a grid without the claimed mirror raises here, before the per-component matrices are built).  eye: the N x N identity.
+        Sweep drivers (keep_coupling=False) with a homogeneous mu never read P, Q, the dense mu matrices or, after the layer's S-matrix, the
+        mode matrices W, V: A = PQ and V = P^-1 W Kz come from E directly (trx_build_a / trx_hmodes).  Not building / not keeping them takes
+        4 of ~16 n^2-sized tensors per sweep point out of the peak: M = Minv = None in the record of such a layer."""
+        eng, cdt = self.engine, self._cdtype
 
         def conv(v, homog):
             if homog:
                 s = self._bvec(v)
                 return s[:, None, None] * eye, (1 / s)[:, None, None] * eye, s
-            g = torch.as_tensor(v, device=self._device)
-            if g.dim() == 2:
-                g = g[None].expand(B, -1, -1)
+            g = self._grid(v)
             if self._general:
                 if diff:
-                    return ag.ConvMatOrdersFn.apply(g.contiguous(), self.orders, cdt, eng), None, None
-                return eng.convmat_orders(g.contiguous(), self._mn_dev, cdt, self._mmax, self._nmax), None, None
+                    return ag.ConvMatOrdersFn.apply(g, self.orders, cdt, eng), None, None
+                return eng.convmat_orders(g, self._mn_dev, cdt, self._mmax, self._nmax), None, None
             if diff:
-                return ag.ConvMatFn.apply(g.contiguous(), self.order[0], self.order[1], cdt, eng), None, None
-            C = eng.convmat(g.contiguous(), self.order[0], self.order[1], cdt)          # rcwa.py:1183-1204
+                return ag.ConvMatFn.apply(g, self.order[0], self.order[1], cdt, eng), None, None
+            C = eng.convmat(g, self.order[0], self.order[1], cdt)                       # rcwa.py:1183-1204
             return C, None, None
 
         def conv_li(v, homog, C):
             """Li's (Cx, Cy) of a patterned grid; a homogeneous layer has Cx = Cy = C (the scaled identity)."""
             if homog:
                 return C, C
-            g = torch.as_tensor(v, device=self._device)
-            if g.dim() == 2:
-                g = g[None].expand(B, -1, -1)
+            g = self._grid(v)
             if diff:
-                return ag.ConvMatLiFn.apply(g.contiguous(), self.order[0], self.order[1], cdt, eng)
-            return eng.convmat_li(g.contiguous(), self.order[0], self.order[1], cdt)[:2]
+                return ag.ConvMatLiFn.apply(g, self.order[0], self.order[1], cdt, eng)
+            return eng.convmat_li(g, self.order[0], self.order[1], cdt)[:2]
 
         def conv_nv(v):
             """(Exx, Exy, Eyy) of a patterned eps grid with the normal-vector rule."""
-            g = torch.as_tensor(v, device=self._device)
-            if g.dim() == 2:
-                g = g[None].expand(B, -1, -1)
-            g = g.contiguous()
+            g = self._grid(v)
             nn = self._nv_products(g, normal_field)
             if self._general:
                 h = self._nv_spacing(g)
@@ -365,14 +459,6 @@ class BatchedRCWA(FluxMixin, VolumeMixin):
                 return self._nv_tensor_torch(g, nn)
             return eng.convmat_nv(g, self.order[0], self.order[1], cdt, sigma=self.nv_sigma, hx=hx, hy=hy, nn=nn)
 
-        if eps_h and mu_h and not diff and not self.keep_coupling and not swept:
-            self._add_homogeneous_layer_bd(thickness, self._bvec(eps), self._bvec(mu))
-            self.symmetry_residual.append(None)
-            self._fold_last_layer()
-            return
-        # Sweep drivers (keep_coupling=False) with a homogeneous mu never read P, Q, the dense mu matrices or, after the layer's
-        # S-matrix, the mode matrices W, V: A = PQ and V = P^-1 W Kz come from E directly (trx_build_a / trx_hmodes).  Not building
-        # / not keeping them takes 4 of ~16 n^2-sized tensors per sweep point out of the peak.
         lean = (not diff) and (not self.keep_coupling) and mu_h and (not eps_h) and (not self.avoid_Pinv_instability)
         E, Einv, eps_s = conv(eps, eps_h)
         if lean:
@@ -382,97 +468,56 @@ class BatchedRCWA(FluxMixin, VolumeMixin):
         plan = None
         if self.symmetry is not None and not (eps_h and mu_h):          # before any heavy work: a grid without the mirror raises here
             plan = self._sym_plan([torch.as_tensor(v, device=self._device) for v, h in ((eps, eps_h), (mu, mu_h)) if not h])
-        li = self.fourier_rule == "li" and not (eps_h and mu_h)
-        Ex, Ey = conv_li(eps, eps_h, E) if li else (None, None)
-        Mx, My = conv_li(mu, mu_h, M) if (li and M is not None) else (None, None)
-        nv = self.fourier_rule == "normal" and not eps_h          # a homogeneous eps has the tensor eps I: Laurent's matrices as they are
-        Exy = None
-        if nv:
-            Ex, Exy, Ey = conv_nv(eps)
-        self.eps_conv.append(E)
-        self.mu_conv.append(M)
-        self.eps_grid.append((self._bvec(eps) if eps_h else eps) if self.keep_coupling else None)
-        self.mu_grid.append((self._bvec(mu) if mu_h else mu) if self.keep_coupling else None)
-        keep_li = li and self.keep_coupling and not eps_h
-        self.eps_conv_x.append(Ex if keep_li else None)
-        self.eps_conv_y.append(Ey if keep_li else None)
-        keep_nv = nv and self.keep_coupling
-        self.eps_conv_xx.append(Ex if keep_nv else None)
-        self.eps_conv_xy.append(Exy if keep_nv else None)
-        self.eps_conv_yy.append(Ey if keep_nv else None)
-        self.layer_N += 1
-        if swept:
-            d = torch.as_tensor(thickness, dtype=self._rdtype, device=self._device)
-            if d.dim() == 1:
-                d = d[None, :].expand(B, -1)
-            if d.dim() != 2 or d.shape[0] != B:
-                raise ValueError(f"add_layer(swept=True): thickness must be [T] or [{B}, T], got {list(d.shape)}")
-            self._swept = dict(index=self.layer_N - 1, d=d.contiguous())
-            self.thickness.append(None)          # no single thickness: see _swept["d"]
-        else:
-            d = self._bvec(thickness, self._rdtype)
-            self.thickness.append(d)
+        exx, exy, eyy, mx, my = E, None, E, M, M
+        if self.fourier_rule == "li" and not (eps_h and mu_h):
+            exx, eyy = conv_li(eps, eps_h, E)
+            if M is not None:
+                mx, my = conv_li(mu, mu_h, M)
+        elif self.fourier_rule == "normal" and not eps_h:      # a homogeneous eps has the tensor eps I: Laurent's matrices as they are
+            exx, exy, eyy = conv_nv(eps)
+        return Medium(E, Einv, M, Minv, eps_s, mu_s, exx, exy, eyy, mx, my), plan
+
+    def _pq(self, fac, diff):
+        """P, Q of a layer (rcwa.py:1226-1232) from its Medium, through the entry of its rule; (None, None) for a lean layer."""
         kxd, kyd = self.Kx_norm_dn, self.Ky_norm_dn
-        inv = (lambda A: ag.InverseFn.apply(A, eng)) if diff else eng.inverse
-        if Einv is None:
-            Einv = inv(E)
-        if Minv is None and M is not None:
-            Minv = inv(M)
         if diff:
-            P, Q = self._pq_torch(E, Einv, M, Minv, kxd, kyd, Ex, Ey, Mx, My, Exy)
-        elif lean:
-            P = Q = None
-        elif nv:
-            P, Q = eng.build_pq_tensor(Ex, Exy, Ey, Einv, M, Minv, kxd, kyd)
-        elif li:
-            P, Q = eng.build_pq_aniso(Ex, Ey, Einv, Mx, My, Minv, kxd, kyd)
-        else:
-            P, Q = eng.build_pq(E, Einv, M, Minv, kxd, kyd)
-        if eps_h and mu_h:                                                              # rcwa.py:1206-1222
-            W = torch.eye(2 * N, dtype=cdt, device=self._device).expand(B, -1, -1).contiguous()
-            kz = torch.sqrt((eps_s * mu_s)[:, None] - kxd ** 2 - kyd ** 2)
-            kz = torch.where(torch.imag(kz) < 0, torch.conj(kz), kz)
-            kz = torch.cat((kz, kz), dim=1)
-        else:                                                                           # rcwa.py:1224-1242
-            if diff:
-                Eig.engine = eng
-                A = ag.GemmFn.apply(P, Q, eng)
-                # stable_eig_grad=False is the reference's plain torch.linalg.eig branch (rcwa.py:1238): its backward is never
-                # broadened.  The choice is bound to this graph node (not to the process-global at backward time).
-                lam, W = Eig.apply(A) if self.stable_eig_grad else Eig.apply(A, Eig.UNBROADENED)
-            else:
-                # A = P Q (rcwa.py:1236): with homogeneous mu the block structure needs two N^3 products, not one (2N)^3
-                if nv:
-                    A = eng.build_a_tensor(Ex, Exy, Ey, Einv, mu_s, kxd, kyd) if mu_h else eng.gemm(P, Q)
-                elif li:
-                    A = eng.build_a_aniso(Ex, Ey, Einv, mu_s, kxd, kyd) if mu_h else eng.gemm(P, Q)
-                else:
-                    A = eng.build_a(E, Einv, mu_s, kxd, kyd) if mu_h else eng.gemm(P, Q)
-                # Li's / the normal-vector matrices live on only in eps_conv_x / _y / _xx / _xy / _yy (keep_coupling)
-                del Einv, Ex, Ey, Mx, My, Exy
-                # mixed-precision eigensolver: two Newton steps for a complex64 problem (1e-5 gate), three for complex128 (engine.eig)
-                steps = 3 if self._dtype == torch.complex128 else 2
-                if plan is None:
-                    lam, W = self._eig_call(A, refine_steps=steps)                          # torch_eig.py:14
-                else:
-                    lam, W, resid = self._eig_folded(A, plan, steps)
-                del A
-            kz = torch.sqrt(lam)
-            kz = torch.where(torch.imag(kz) < 0, -kz, kz)                               # rcwa.py:1241
-        self.symmetry_residual.append(resid if plan is not None else None)
-        self.P.append(P)
-        self.Q.append(Q)
-        self.kz_norm.append(kz)
-        self.E_eigvec.append(W)
-        self._mu_scalar = mu_s if mu_h else None       # homogeneous mu: V = P^-1 W Kz from the rank-N structure of P (trx_hmodes)
-        if swept:
-            self._keep_swept_modes()
-            return
-        if diff:
-            self._solve_layer_smatrix_diff()
-        else:
-            self._solve_layer_smatrix()
-        self._fold_last_layer()
+            return self._pq_torch(fac.E, fac.Einv, fac.M, fac.Minv, kxd, kyd, fac.exx, fac.eyy, fac.mx, fac.my, fac.exy)
+        if fac.M is None:
+            return None, None
+        eng = self.engine
+        if fac.exy is not None:
+            return eng.build_pq_tensor(fac.exx, fac.exy, fac.eyy, fac.Einv, fac.M, fac.Minv, kxd, kyd)
+        if fac.exx is not fac.E or fac.mx is not fac.M:
+            return eng.build_pq_aniso(fac.exx, fac.eyy, fac.Einv, fac.mx, fac.my, fac.Minv, kxd, kyd)
+        return eng.build_pq(fac.E, fac.Einv, fac.M, fac.Minv, kxd, kyd)
+
+    def _a(self, fac, P, Q):
+        """A = P Q (rcwa.py:1236): with a homogeneous mu the block structure needs two N^3 products, not one (2N)^3."""
+        eng, kxd, kyd = self.engine, self.Kx_norm_dn, self.Ky_norm_dn
+        if fac.mu_s is None:
+            return eng.gemm(P, Q)
+        if fac.exy is not None:
+            return eng.build_a_tensor(fac.exx, fac.exy, fac.eyy, fac.Einv, fac.mu_s, kxd, kyd)
+        if fac.exx is not fac.E:
+            return eng.build_a_aniso(fac.exx, fac.eyy, fac.Einv, fac.mu_s, kxd, kyd)
+        return eng.build_a(fac.E, fac.Einv, fac.mu_s, kxd, kyd)
+
+    def _drop_layer_matrices(self, i, modes=False):
+        """The convolution matrices of a folded layer are not read again; modes: nor are the P, Q its modes came from (the swept layer)."""
+        self.eps_conv[i] = None
+        self.eps_conv_x[i] = self.eps_conv_y[i] = None
+        self.eps_conv_xx[i] = self.eps_conv_xy[i] = self.eps_conv_yy[i] = None
+        if modes:
+            self.P[i] = self.Q[i] = None
+
+    @staticmethod
+    def _append_none(*lists):
+        for lst in lists:
+            lst.append(None)
+
+    def _pack_bd(self, S):
+        """Four BlockDiag2 blocks -> [4,4,B,N] diagonals in the compute dtype, as the library takes a block-diagonal S-matrix."""
+        return torch.stack([torch.stack(blk.d, dim=0) for blk in S], dim=0).to(self._cdtype).contiguous()
 
     def _fold_last_layer(self):
         """Streaming cascade: fold the layer just added into the running star product and drop it.  Decided PER LAYER: a layer is folded
@@ -487,9 +532,7 @@ class BatchedRCWA(FluxMixin, VolumeMixin):
                 S = self._layer_S(i)
                 self._right_running = S if self._right_running is None else self._star(self._right_running, S, [[], []], [[], []])[0]
                 self.layer_S11[i] = self.layer_S21[i] = None
-                self.eps_conv[i] = None
-                self.eps_conv_x[i] = self.eps_conv_y[i] = None
-                self.eps_conv_xx[i] = self.eps_conv_xy[i] = self.eps_conv_yy[i] = None
+                self._drop_layer_matrices(i)
                 self._n_right_folded += 1
             return
         if not self.fold_layers or getattr(self, "_diff", False) or self._n_folded != i:
@@ -500,9 +543,7 @@ class BatchedRCWA(FluxMixin, VolumeMixin):
         else:
             self._running, _ = self._star(self._running, S, [[], []], [[], []])
         self.layer_S11[i] = self.layer_S21[i] = None
-        self.eps_conv[i] = None
-        self.eps_conv_x[i] = self.eps_conv_y[i] = None
-        self.eps_conv_xx[i] = self.eps_conv_xy[i] = self.eps_conv_yy[i] = None
+        self._drop_layer_matrices(i)
         self._n_folded = i + 1
 
     def _keep_swept_modes(self):
@@ -514,13 +555,9 @@ class BatchedRCWA(FluxMixin, VolumeMixin):
         else:
             V = eng.solve(self.P[-1], W * kz[:, None, :])
         self.H_eigvec.append(V)
-        for lst in (self.layer_S11, self.layer_S21, self.Cplus, self.Cminus):
-            lst.append(None)
+        self._append_none(self.layer_S11, self.layer_S21, self.Cplus, self.Cminus)
         if self.fold_layers:              # as a folded layer: the matrices the modes came from are not read again
-            i = self.layer_N - 1
-            self.eps_conv[i] = self.P[i] = self.Q[i] = None
-            self.eps_conv_x[i] = self.eps_conv_y[i] = None
-            self.eps_conv_xx[i] = self.eps_conv_xy[i] = self.eps_conv_yy[i] = None
+            self._drop_layer_matrices(self.layer_N - 1, modes=True)
 
     def _swept_sides(self):
         """(Lft, Rgt): everything left / right of the swept layer as one S-matrix each -- None (nothing there), a list of four BlockDiag2
@@ -554,7 +591,7 @@ class BatchedRCWA(FluxMixin, VolumeMixin):
         ops = []
         for S in self._swept_sides():
             if S is not None and self._is_bd(S):
-                S = torch.stack([torch.stack(blk.d, dim=0) for blk in S], dim=0).to(self._cdtype).contiguous()          # [4,4,B,N]
+                S = self._pack_bd(S)
             ops.append(S)
         vfinv = torch.stack(self._Vfinv.d, dim=0).to(self._cdtype).contiguous()                                         # [4,B,N]
         prep = self.engine.thickness_prepare(self.E_eigvec[i], self.H_eigvec[i], vfinv, ops[0], ops[1], 0 if k < 2 else 1, cols)
@@ -572,26 +609,6 @@ class BatchedRCWA(FluxMixin, VolumeMixin):
         if self._swept is not None:
             raise ValueError(f"{what} is not available on a solver with a swept layer (add_layer(..., swept=True)): there is no single stack to "
                              "solve; solve_S_parameters(...) returns the S-parameters of every thickness")
-
-    def power_flux(self, *a, **kw):
-        self._refuse_swept("power_flux")
-        return super().power_flux(*a, **kw)
-
-    def incident_flux(self, *a, **kw):
-        self._refuse_swept("incident_flux")
-        return super().incident_flux(*a, **kw)
-
-    def absorption(self, *a, **kw):
-        self._refuse_swept("absorption")
-        return super().absorption(*a, **kw)
-
-    def volume_integral(self, *a, **kw):
-        self._refuse_swept("volume_integral")
-        return super().volume_integral(*a, **kw)
-
-    def absorption_by_region(self, *a, **kw):
-        self._refuse_swept("absorption_by_region")
-        return super().absorption_by_region(*a, **kw)
 
     def _add_homogeneous_layer_bd(self, thickness, eps_s, mu_s):
         """Homogeneous layer without field bookkeeping (keep_coupling=False): every operator of rcwa.py:1206-1222 and 1244-1281
@@ -616,9 +633,8 @@ class BatchedRCWA(FluxMixin, VolumeMixin):
         self.layer_N += 1
         self.thickness.append(d)
         self.kz_norm.append(torch.cat((kz, kz), dim=1))
-        for lst in (self.eps_conv, self.mu_conv, self.eps_grid, self.mu_grid, self.eps_conv_x, self.eps_conv_y, self.eps_conv_xx, self.eps_conv_xy, self.eps_conv_yy,
-                    self.P, self.Q, self.E_eigvec, self.H_eigvec, self.Cplus, self.Cminus):
-            lst.append(None)
+        self._append_none(self.eps_conv, self.mu_conv, self.eps_grid, self.mu_grid, self.eps_conv_x, self.eps_conv_y, self.eps_conv_xx, self.eps_conv_xy,
+                          self.eps_conv_yy, self.P, self.Q, self.E_eigvec, self.H_eigvec, self.Cplus, self.Cminus)
 
     def _nv_spacing(self, g):
         """Grid spacings (hx, hy) of a [B, nx, ny] grid over the unit cell: they orient the gradient of the normal-vector field.  On the
@@ -839,7 +855,7 @@ class BatchedRCWA(FluxMixin, VolumeMixin):
         if getattr(self, "_diff", False):
             dense = [blk.dense().to(self._cdtype) for blk in Sbd]
             return self._RS_prod_diff(dense, S, [[], []], C) if side == 0 else self._RS_prod_diff(S, dense, C, [[], []])
-        bd = torch.stack([torch.stack(blk.d, dim=0) for blk in Sbd], dim=0).to(self._cdtype).contiguous()   # [4,4,B,N]
+        bd = self._pack_bd(Sbd)
         Sn, X1, X2, Y1, Y2 = eng.redheffer_halfspace(side, bd, S, want_xy=len(C[0]) > 0)
         Cn = [[], []]
         if side == 0:                       # C belongs to the right operand (rcwa.py:1302-1304)
@@ -942,7 +958,7 @@ class BatchedRCWA(FluxMixin, VolumeMixin):
             return self._sparam_values(lambda c: Sk[:, :, c], k, oi, ri, polarization, power_norm, evanscent)
         cols = self._sparam_columns(ri, polarization)
         Sbd = self._Sin if side == 0 else self._Sout
-        bd = torch.stack([torch.stack(blk.d, dim=0) for blk in Sbd], dim=0).to(self._cdtype).contiguous()   # [4,4,B,N]
+        bd = self._pack_bd(Sbd)
         out = self.engine.redheffer_halfspace_columns(side, bd, S, k, cols)             # [B, n, len(cols)]
         return self._sparam_values(lambda c: out[:, :, cols.index(c)], k, oi, ri, polarization, power_norm, evanscent)
 
@@ -1100,3 +1116,16 @@ class BatchedRCWA(FluxMixin, VolumeMixin):
         if unit == "degree":
             inc, azi = (180. / PI_REF) * inc, (180. / PI_REF) * azi
         return inc, azi
+
+
+def _refusing_swept(name):
+    """The mixin method `name`, refused on a solver with a swept layer."""
+    def method(self, *a, **kw):
+        self._refuse_swept(name)
+        return getattr(super(BatchedRCWA, self), name)(*a, **kw)
+    method.__name__ = name
+    return method
+
+
+for _name in ("power_flux", "incident_flux", "absorption", "volume_integral", "absorption_by_region"):
+    setattr(BatchedRCWA, _name, _refusing_swept(_name))

@@ -14,7 +14,6 @@
 //   3. the transform of U along the other axis as the library's batched GEMM  F_b = U_b^T W  ([w^2, ny] x [ny, 4o'+1]), accumulated
 //      over chunks of rows when the caller does not keep U (the chunk bounds the workspace);
 //   4. scatter of F, G into E_x, E_y [B,N,N] in the compute dtype.
-// Also here: P, Q and A = PQ of a layer whose electric (and magnetic) convolution matrices differ per field component.
 #include <algorithm>
 
 #include "common.hpp"
@@ -285,78 +284,6 @@ int convmat_li_t(int cplx, const void* grid, int batch, int nx, int ny, int ox, 
     return TRX_OK;
 }
 
-// ---- P, Q and A = PQ with per-component convolution matrices ------------------------------------------------------------------------
-// P = [[Kx Ei Ky, My - Kx Ei Kx], [Ky Ei Ky - Mx, -Ky Ei Kx]],  Q = [[-Kx Mi Ky, Kx Mi Kx - Ey], [Ex - Ky Mi Ky, Ky Mi Kx]]
-template <class T>
-__global__ __launch_bounds__(256) void build_pq_aniso_kernel(const cx<T>* __restrict__ Ex, const cx<T>* __restrict__ Ey,
-                                                             const cx<T>* __restrict__ Ei, const cx<T>* __restrict__ Mx,
-                                                             const cx<T>* __restrict__ My, const cx<T>* __restrict__ Mi,
-                                                             const cx<T>* __restrict__ kx, const cx<T>* __restrict__ ky, int N,
-                                                             cx<T>* __restrict__ P, cx<T>* __restrict__ Q) {
-    const int b = blockIdx.z, i = blockIdx.y;
-    const int j = blockIdx.x * blockDim.x + threadIdx.x;
-    if (j >= N) return;
-    const long o = ((long)b * N + i) * N + j;
-    const cx<T> ex = Ex[o], ey = Ey[o], ei = Ei[o], mx = Mx[o], my = My[o], mi = Mi[o];
-    const cx<T> kxi = kx[(long)b * N + i], kyi = ky[(long)b * N + i], kxj = kx[(long)b * N + j], kyj = ky[(long)b * N + j];
-    const int n = 2 * N;
-    cx<T>* Pb = P + (long)b * n * n;
-    cx<T>* Qb = Q + (long)b * n * n;
-    const long r0 = (long)i * n + j, r1 = (long)(i + N) * n + j;
-    Pb[r0] = kxi * ei * kyj;
-    Pb[r0 + N] = my - kxi * ei * kxj;
-    Pb[r1] = kyi * ei * kyj - mx;
-    Pb[r1 + N] = -(kyi * ei * kxj);
-    Qb[r0] = -(kxi * mi * kyj);
-    Qb[r0 + N] = kxi * mi * kxj - ey;
-    Qb[r1] = ex - kyi * mi * kyj;
-    Qb[r1 + N] = kyi * mi * kxj;
-}
-
-// A = PQ for homogeneous mu:  [[mu Ex - Ky^2 - Kx Gx, KxKy - Kx Gy], [KxKy - Ky Gx, mu Ey - Kx^2 - Ky Gy]],  Gx = Ei (Kx Ex), Gy = Ei (Ky Ey)
-template <class T>
-__global__ __launch_bounds__(256) void li_scale_rows_kernel(const cx<T>* __restrict__ in, const cx<T>* __restrict__ s, int N, cx<T>* __restrict__ out) {
-    const int b = blockIdx.z, i = blockIdx.y;
-    const int j = blockIdx.x * blockDim.x + threadIdx.x;
-    if (j >= N) return;
-    const long o = ((long)b * N + i) * N + j;
-    out[o] = s[(long)b * N + i] * in[o];
-}
-template <class T>
-__global__ __launch_bounds__(256) void assemble_a_aniso_kernel(const cx<T>* __restrict__ Ex, const cx<T>* __restrict__ Ey, const cx<T>* __restrict__ Gx,
-                                                               const cx<T>* __restrict__ Gy, const cx<T>* __restrict__ mu, const cx<T>* __restrict__ kx,
-                                                               const cx<T>* __restrict__ ky, int N, cx<T>* __restrict__ A) {
-    const int b = blockIdx.z, i = blockIdx.y;
-    const int j = blockIdx.x * blockDim.x + threadIdx.x;
-    if (j >= N) return;
-    const long o = ((long)b * N + i) * N + j;
-    const cx<T> kxi = kx[(long)b * N + i], kyi = ky[(long)b * N + i];
-    const cx<T> ex = mu[b] * Ex[o], ey = mu[b] * Ey[o], gx = Gx[o], gy = Gy[o];
-    const int n = 2 * N;
-    cx<T>* Ab = A + (long)b * n * n;
-    cx<T> a11 = ex - kxi * gx, a12 = -(kxi * gy), a21 = -(kyi * gx), a22 = ey - kyi * gy;
-    if (i == j) { a11 -= kyi * kyi; a22 -= kxi * kxi; a12 += kxi * kyi; a21 += kxi * kyi; }
-    Ab[(long)i * n + j] = a11;
-    Ab[(long)i * n + j + N] = a12;
-    Ab[(long)(i + N) * n + j] = a21;
-    Ab[(long)(i + N) * n + j + N] = a22;
-}
-template <class T>
-int build_a_aniso_t(hipStream_t s, const cx<T>* Ex, const cx<T>* Ey, const cx<T>* Ei, const cx<T>* mu, const cx<T>* kx, const cx<T>* ky, int N,
-                    int batch, cx<T>* A, cx<T>* ws) {
-    const long NN = (long)N * N, bNN = (long)batch * NN;
-    const cx<T> one(T(1), T(0)), zero(T(0), T(0));
-    const dim3 g(cdiv_i(N, 256), N, batch), blk(256);
-    cx<T>*Sx = ws, *Gx = ws + bNN, *Gy = ws + 2 * bNN;
-    TRX_LAUNCH((li_scale_rows_kernel<T>), g, blk, 0, s, Ex, kx, N, Sx);
-    int rc = gemm<T>(s, TRX_OP_N, TRX_OP_N, N, N, N, one, Ei, N, NN, Sx, N, NN, zero, Gx, N, NN, batch); if (rc) return rc;
-    TRX_LAUNCH((li_scale_rows_kernel<T>), g, blk, 0, s, Ey, ky, N, Sx);
-    rc = gemm<T>(s, TRX_OP_N, TRX_OP_N, N, N, N, one, Ei, N, NN, Sx, N, NN, zero, Gy, N, NN, batch); if (rc) return rc;
-    TRX_LAUNCH((assemble_a_aniso_kernel<T>), g, blk, 0, s, Ex, Ey, (const cx<T>*)Gx, (const cx<T>*)Gy, mu, kx, ky, N, A);
-    TRX_CHECK_LAUNCH();
-    return TRX_OK;
-}
-
 }  // namespace
 }  // namespace trx
 
@@ -379,40 +306,4 @@ extern "C" int trx_convmat_li(int dtype, int grid_is_complex, const void* grid, 
     hipStream_t s = trx::api_stream(stream);
     if (dtype == TRX_C64) return convmat_li_t<float>(grid_is_complex, grid, batch, nx, ny, ox, oy, Ex, Ey, Ux, Uy, info, ws, dtype, s);
     return convmat_li_t<double>(grid_is_complex, grid, batch, nx, ny, ox, oy, Ex, Ey, Ux, Uy, info, ws, dtype, s);
-}
-
-extern "C" int trx_build_pq_aniso(int dtype, const void* Ex, const void* Ey, const void* Einv, const void* Mx, const void* My, const void* Minv,
-                                  const void* kx, const void* ky, int N, int batch, void* P, void* Q, void* stream) {
-    if (!Ex || !Ey || !Einv || !Mx || !My || !Minv || !kx || !ky || !P || !Q || N <= 0 || batch <= 0) return TRX_ERR_ARG;
-    hipStream_t s = trx::api_stream(stream);
-    const dim3 g(cdiv_i(N, 256), N, batch), blk(256);
-    if (dtype == TRX_C64)
-        TRX_LAUNCH((build_pq_aniso_kernel<float>), g, blk, 0, s, (const cx<float>*)Ex, (const cx<float>*)Ey, (const cx<float>*)Einv, (const cx<float>*)Mx,
-                   (const cx<float>*)My, (const cx<float>*)Minv, (const cx<float>*)kx, (const cx<float>*)ky, N, (cx<float>*)P, (cx<float>*)Q);
-    else if (dtype == TRX_C128)
-        TRX_LAUNCH((build_pq_aniso_kernel<double>), g, blk, 0, s, (const cx<double>*)Ex, (const cx<double>*)Ey, (const cx<double>*)Einv,
-                   (const cx<double>*)Mx, (const cx<double>*)My, (const cx<double>*)Minv, (const cx<double>*)kx, (const cx<double>*)ky, N,
-                   (cx<double>*)P, (cx<double>*)Q);
-    else
-        return TRX_ERR_DTYPE;
-    TRX_CHECK_LAUNCH();
-    return TRX_OK;
-}
-
-extern "C" size_t trx_build_a_aniso_ws_bytes(int dtype, int N, int batch) {
-    return (size_t)(dtype == TRX_C128 ? 16 : 8) * 3 * (size_t)batch * N * N;
-}
-
-extern "C" int trx_build_a_aniso(int dtype, const void* Ex, const void* Ey, const void* Einv, const void* mu, const void* kx, const void* ky, int N,
-                                 int batch, void* A, void* ws, size_t ws_bytes, void* stream) {
-    if (!Ex || !Ey || !Einv || !mu || !kx || !ky || !A || !ws || N <= 0 || batch <= 0) return TRX_ERR_ARG;
-    if (ws_bytes < trx_build_a_aniso_ws_bytes(dtype, N, batch)) return TRX_ERR_WORKSPACE;
-    hipStream_t s = trx::api_stream(stream);
-    if (dtype == TRX_C64)
-        return build_a_aniso_t<float>(s, (const cx<float>*)Ex, (const cx<float>*)Ey, (const cx<float>*)Einv, (const cx<float>*)mu, (const cx<float>*)kx,
-                                      (const cx<float>*)ky, N, batch, (cx<float>*)A, (cx<float>*)ws);
-    if (dtype == TRX_C128)
-        return build_a_aniso_t<double>(s, (const cx<double>*)Ex, (const cx<double>*)Ey, (const cx<double>*)Einv, (const cx<double>*)mu,
-                                       (const cx<double>*)kx, (const cx<double>*)ky, N, batch, (cx<double>*)A, (cx<double>*)ws);
-    return TRX_ERR_DTYPE;
 }

@@ -17,7 +17,6 @@
 //      (the fallback chosen by the study in profiles/normal_vector.txt).
 // trx_convmat_nv chains the field, trx_convmat of eps, of 1/eps and of the three product grids, the inverse of [1/eps] (trx_inverse,
 // complex128) and the six GEMMs of the three symmetrised products; all of it in fp64 for both dtypes.
-// Also here: P, Q and A = PQ of a layer whose in-plane permittivity is the full tensor.
 #include <algorithm>
 #include <cmath>
 
@@ -293,85 +292,6 @@ int convmat_nv_t(int cplx, const void* grid, int batch, int nx, int ny, int ox, 
     return TRX_OK;
 }
 
-// ---- P, Q and A = PQ with the in-plane permittivity tensor ---------------------------------------------------------------------------
-// P = [[Kx Ei Ky, M - Kx Ei Kx], [Ky Ei Ky - M, -Ky Ei Kx]],  Q = [[-Kx Mi Ky - Exy, Kx Mi Kx - Eyy], [Exx - Ky Mi Ky, Ky Mi Kx + Exy]]
-template <class T>
-__global__ __launch_bounds__(256) void build_pq_tensor_kernel(const cx<T>* __restrict__ Exx, const cx<T>* __restrict__ Exy,
-                                                              const cx<T>* __restrict__ Eyy, const cx<T>* __restrict__ Ei,
-                                                              const cx<T>* __restrict__ M, const cx<T>* __restrict__ Mi,
-                                                              const cx<T>* __restrict__ kx, const cx<T>* __restrict__ ky, int N,
-                                                              cx<T>* __restrict__ P, cx<T>* __restrict__ Q) {
-    const int b = blockIdx.z, i = blockIdx.y;
-    const int j = blockIdx.x * blockDim.x + threadIdx.x;
-    if (j >= N) return;
-    const long o = ((long)b * N + i) * N + j;
-    const cx<T> exx = Exx[o], exy = Exy[o], eyy = Eyy[o], ei = Ei[o], m = M[o], mi = Mi[o];
-    const cx<T> kxi = kx[(long)b * N + i], kyi = ky[(long)b * N + i], kxj = kx[(long)b * N + j], kyj = ky[(long)b * N + j];
-    const int n = 2 * N;
-    cx<T>* Pb = P + (long)b * n * n;
-    cx<T>* Qb = Q + (long)b * n * n;
-    const long r0 = (long)i * n + j, r1 = (long)(i + N) * n + j;
-    Pb[r0] = kxi * ei * kyj;
-    Pb[r0 + N] = m - kxi * ei * kxj;
-    Pb[r1] = kyi * ei * kyj - m;
-    Pb[r1 + N] = -(kyi * ei * kxj);
-    Qb[r0] = -(kxi * mi * kyj) - exy;
-    Qb[r0 + N] = kxi * mi * kxj - eyy;
-    Qb[r1] = exx - kyi * mi * kyj;
-    Qb[r1 + N] = kyi * mi * kxj + exy;
-}
-
-// A = PQ for homogeneous mu:
-//   [[mu Exx - Ky^2 - Kx Gx, mu Exy + Kx Ky - Kx Gy], [mu Exy + Kx Ky - Ky Gx, mu Eyy - Kx^2 - Ky Gy]],
-//   [Gx, Gy] = Ei S,  S = [Kx Exx + Ky Exy, Kx Exy + Ky Eyy]   (one N x 2N product)
-template <class T>
-__global__ __launch_bounds__(256) void nv_s_kernel(const cx<T>* __restrict__ Exx, const cx<T>* __restrict__ Exy, const cx<T>* __restrict__ Eyy,
-                                                   const cx<T>* __restrict__ kx, const cx<T>* __restrict__ ky, int N, cx<T>* __restrict__ S) {
-    const int b = blockIdx.z, i = blockIdx.y;
-    const int j = blockIdx.x * blockDim.x + threadIdx.x;
-    if (j >= N) return;
-    const long o = ((long)b * N + i) * N + j;
-    const cx<T> kxi = kx[(long)b * N + i], kyi = ky[(long)b * N + i], exy = Exy[o];
-    cx<T>* Sr = S + ((long)b * N + i) * 2 * N;
-    Sr[j] = kxi * Exx[o] + kyi * exy;
-    Sr[j + N] = kxi * exy + kyi * Eyy[o];
-}
-template <class T>
-__global__ __launch_bounds__(256) void assemble_a_tensor_kernel(const cx<T>* __restrict__ Exx, const cx<T>* __restrict__ Exy,
-                                                                const cx<T>* __restrict__ Eyy, const cx<T>* __restrict__ G,
-                                                                const cx<T>* __restrict__ mu, const cx<T>* __restrict__ kx,
-                                                                const cx<T>* __restrict__ ky, int N, cx<T>* __restrict__ A) {
-    const int b = blockIdx.z, i = blockIdx.y;
-    const int j = blockIdx.x * blockDim.x + threadIdx.x;
-    if (j >= N) return;
-    const long o = ((long)b * N + i) * N + j;
-    const cx<T> kxi = kx[(long)b * N + i], kyi = ky[(long)b * N + i], m = mu[b];
-    const cx<T>* Gr = G + ((long)b * N + i) * 2 * N;
-    const cx<T> gx = Gr[j], gy = Gr[j + N], mxy = m * Exy[o];
-    const int n = 2 * N;
-    cx<T>* Ab = A + (long)b * n * n;
-    cx<T> a11 = m * Exx[o] - kxi * gx, a12 = mxy - kxi * gy, a21 = mxy - kyi * gx, a22 = m * Eyy[o] - kyi * gy;
-    if (i == j) { a11 -= kyi * kyi; a22 -= kxi * kxi; a12 += kxi * kyi; a21 += kxi * kyi; }
-    Ab[(long)i * n + j] = a11;
-    Ab[(long)i * n + j + N] = a12;
-    Ab[(long)(i + N) * n + j] = a21;
-    Ab[(long)(i + N) * n + j + N] = a22;
-}
-template <class T>
-int build_a_tensor_t(hipStream_t s, const cx<T>* Exx, const cx<T>* Exy, const cx<T>* Eyy, const cx<T>* Ei, const cx<T>* mu, const cx<T>* kx,
-                     const cx<T>* ky, int N, int batch, cx<T>* A, cx<T>* ws) {
-    const long NN = (long)N * N, bNN2 = 2L * batch * NN;
-    const cx<T> one(T(1), T(0)), zero(T(0), T(0));
-    const dim3 g(cdiv_i(N, 256), N, batch), blk(256);
-    cx<T>*S = ws, *G = ws + bNN2;
-    TRX_LAUNCH((nv_s_kernel<T>), g, blk, 0, s, Exx, Exy, Eyy, kx, ky, N, S);
-    int rc = gemm<T>(s, TRX_OP_N, TRX_OP_N, N, 2 * N, N, one, Ei, N, NN, S, 2 * N, 2 * NN, zero, G, 2 * N, 2 * NN, batch);
-    if (rc) return rc;
-    TRX_LAUNCH((assemble_a_tensor_kernel<T>), g, blk, 0, s, Exx, Exy, Eyy, (const cx<T>*)G, mu, kx, ky, N, A);
-    TRX_CHECK_LAUNCH();
-    return TRX_OK;
-}
-
 }  // namespace
 }  // namespace trx
 
@@ -475,42 +395,4 @@ extern "C" int trx_convmat_nv_orders(int dtype, int grid_is_complex, const void*
                                    mn, N, rect ? nullptr : hinv);
     return convmat_nv_t<double>(grid_is_complex, grid, batch, n1, n2, mmax, nmax, sigma, hx, hy, nn, Exx, Exy, Eyy, info, (char*)ws, dtype, s,
                                 mn, N, rect ? nullptr : hinv);
-}
-
-extern "C" int trx_build_pq_tensor(int dtype, const void* Exx, const void* Exy, const void* Eyy, const void* Einv, const void* Mu,
-                                   const void* Muinv, const void* kx, const void* ky, int N, int batch, void* P, void* Q, void* stream) {
-    if (!Exx || !Exy || !Eyy || !Einv || !Mu || !Muinv || !kx || !ky || !P || !Q || N <= 0 || batch <= 0) return TRX_ERR_ARG;
-    hipStream_t s = trx::api_stream(stream);
-    const dim3 g(cdiv_i(N, 256), N, batch), blk(256);
-    if (dtype == TRX_C64)
-        TRX_LAUNCH((build_pq_tensor_kernel<float>), g, blk, 0, s, (const cx<float>*)Exx, (const cx<float>*)Exy, (const cx<float>*)Eyy,
-                   (const cx<float>*)Einv, (const cx<float>*)Mu, (const cx<float>*)Muinv, (const cx<float>*)kx, (const cx<float>*)ky, N,
-                   (cx<float>*)P, (cx<float>*)Q);
-    else if (dtype == TRX_C128)
-        TRX_LAUNCH((build_pq_tensor_kernel<double>), g, blk, 0, s, (const cx<double>*)Exx, (const cx<double>*)Exy, (const cx<double>*)Eyy,
-                   (const cx<double>*)Einv, (const cx<double>*)Mu, (const cx<double>*)Muinv, (const cx<double>*)kx, (const cx<double>*)ky, N,
-                   (cx<double>*)P, (cx<double>*)Q);
-    else
-        return TRX_ERR_DTYPE;
-    TRX_CHECK_LAUNCH();
-    return TRX_OK;
-}
-
-extern "C" size_t trx_build_a_tensor_ws_bytes(int dtype, int N, int batch) {
-    return (size_t)(dtype == TRX_C128 ? 16 : 8) * 4 * (size_t)batch * N * N;
-}
-
-extern "C" int trx_build_a_tensor(int dtype, const void* Exx, const void* Exy, const void* Eyy, const void* Einv, const void* mu, const void* kx,
-                                  const void* ky, int N, int batch, void* A, void* ws, size_t ws_bytes, void* stream) {
-    if (!Exx || !Exy || !Eyy || !Einv || !mu || !kx || !ky || !A || !ws || N <= 0 || batch <= 0) return TRX_ERR_ARG;
-    if (ws_bytes < trx_build_a_tensor_ws_bytes(dtype, N, batch)) return TRX_ERR_WORKSPACE;
-    hipStream_t s = trx::api_stream(stream);
-    if (dtype == TRX_C64)
-        return build_a_tensor_t<float>(s, (const cx<float>*)Exx, (const cx<float>*)Exy, (const cx<float>*)Eyy, (const cx<float>*)Einv,
-                                       (const cx<float>*)mu, (const cx<float>*)kx, (const cx<float>*)ky, N, batch, (cx<float>*)A, (cx<float>*)ws);
-    if (dtype == TRX_C128)
-        return build_a_tensor_t<double>(s, (const cx<double>*)Exx, (const cx<double>*)Exy, (const cx<double>*)Eyy, (const cx<double>*)Einv,
-                                        (const cx<double>*)mu, (const cx<double>*)kx, (const cx<double>*)ky, N, batch, (cx<double>*)A,
-                                        (cx<double>*)ws);
-    return TRX_ERR_DTYPE;
 }

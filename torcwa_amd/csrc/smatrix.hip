@@ -1,6 +1,6 @@
-// Layer eigenproblem assembly, layer scattering matrix and Redheffer star product (batched, row-major complex).
-// Replaces torcwa/rcwa.py:1224-1232 (`_eigen_decomposition`: P, Q), :1244-1281 (`_solve_layer_smatrix`) and
-// :1283-1306 (`_RS_prod`) with the lean formulation of SURVEY.md section 7.2, which is algebraically identical:
+// Layer scattering matrix and Redheffer star product (batched, row-major complex; the eigenproblem assembly is assembly.hip).
+// Replaces torcwa/rcwa.py:1244-1281 (`_solve_layer_smatrix`) and :1283-1306 (`_RS_prod`) with the lean formulation of
+// SURVEY.md section 7.2, which is algebraically identical:
 //
 //   * Kx, Ky, Kz, X=exp(i w kz d), Vf are (block-)diagonal: they are never materialised, every product with them
 //     is a fused row/column scaling inside an assembly kernel.
@@ -11,32 +11,6 @@
 
 namespace trx {
 namespace {
-
-// P = [[Kx Ei Ky, M - Kx Ei Kx], [Ky Ei Ky - M, -Ky Ei Kx]],  Q = [[-Kx Mi Ky, Kx Mi Kx - E], [E - Ky Mi Ky, Ky Mi Kx]]
-template <class T>
-__global__ __launch_bounds__(256) void build_pq_kernel(const cx<T>* __restrict__ E, const cx<T>* __restrict__ Ei,
-                                                       const cx<T>* __restrict__ M, const cx<T>* __restrict__ Mi,
-                                                       const cx<T>* __restrict__ kx, const cx<T>* __restrict__ ky, int N,
-                                                       cx<T>* __restrict__ P, cx<T>* __restrict__ Q) {
-    const int b = blockIdx.z, i = blockIdx.y;
-    const int j = blockIdx.x * blockDim.x + threadIdx.x;
-    if (j >= N) return;
-    const long o = ((long)b * N + i) * N + j;
-    const cx<T> e = E[o], ei = Ei[o], m = M[o], mi = Mi[o];
-    const cx<T> kxi = kx[(long)b * N + i], kyi = ky[(long)b * N + i], kxj = kx[(long)b * N + j], kyj = ky[(long)b * N + j];
-    const int n = 2 * N;
-    cx<T>* Pb = P + (long)b * n * n;
-    cx<T>* Qb = Q + (long)b * n * n;
-    const long r0 = (long)i * n + j, r1 = (long)(i + N) * n + j;
-    Pb[r0] = kxi * ei * kyj;
-    Pb[r0 + N] = m - kxi * ei * kxj;
-    Pb[r1] = kyi * ei * kyj - m;
-    Pb[r1 + N] = -(kyi * ei * kxj);
-    Qb[r0] = -(kxi * mi * kyj);
-    Qb[r0 + N] = kxi * mi * kxj - e;
-    Qb[r1] = e - kyi * mi * kyj;
-    Qb[r1 + N] = kyi * mi * kxj;
-}
 
 // out[i,j] = in[i,j] * s[j]
 template <class T>
@@ -158,14 +132,6 @@ __global__ __launch_bounds__(256) void layer_R_kernel(const cx<T>* __restrict__ 
     const cx<T> wx = w * xj;
     Rp[o] = w + wx;
     Rm[o] = w - wx;
-}
-
-template <class T>
-int build_pq_t(hipStream_t s, const void* E, const void* Ei, const void* M, const void* Mi, const void* kx, const void* ky, int N, int batch, void* P, void* Q) {
-    TRX_LAUNCH((build_pq_kernel<T>), dim3(cdiv_i(N, 256), N, batch), dim3(256), 0, s, (const cx<T>*)E, (const cx<T>*)Ei, (const cx<T>*)M, (const cx<T>*)Mi,
-               (const cx<T>*)kx, (const cx<T>*)ky, N, (cx<T>*)P, (cx<T>*)Q);
-    TRX_CHECK_LAUNCH();
-    return TRX_OK;
 }
 
 // ---- V = P^-1 (W Kz) through the rank-N structure of P (homogeneous mu) -------------------------------------------------
@@ -598,64 +564,10 @@ int redheffer_halfspace_columns_t(hipStream_t s, int dtype, int side, const cx<T
     return TRX_OK;
 }
 
-// A = P Q for a layer with homogeneous mu (rcwa.py:1236), from the block structure
-//   A = [[mu E - Ky^2 - Kx Gx,  KxKy - Kx Gy], [KxKy - Ky Gx,  mu E - Kx^2 - Ky Gy]],  Gx = E^-1 (Kx E), Gy = E^-1 (Ky E)
-// i.e. two N^3 products instead of one (2N)^3 product.
-template <class T>
-__global__ __launch_bounds__(256) void scale_rows_kernel(const cx<T>* __restrict__ in, const cx<T>* __restrict__ s, int N, cx<T>* __restrict__ out) {
-    const int b = blockIdx.z, i = blockIdx.y;
-    const int j = blockIdx.x * blockDim.x + threadIdx.x;
-    if (j >= N) return;
-    const long o = ((long)b * N + i) * N + j;
-    out[o] = s[(long)b * N + i] * in[o];
-}
-template <class T>
-__global__ __launch_bounds__(256) void assemble_a_kernel(const cx<T>* __restrict__ E, const cx<T>* __restrict__ Gx, const cx<T>* __restrict__ Gy,
-                                                         const cx<T>* __restrict__ mu, const cx<T>* __restrict__ kx, const cx<T>* __restrict__ ky, int N,
-                                                         cx<T>* __restrict__ A) {
-    const int b = blockIdx.z, i = blockIdx.y;
-    const int j = blockIdx.x * blockDim.x + threadIdx.x;
-    if (j >= N) return;
-    const long o = ((long)b * N + i) * N + j;
-    const cx<T> kxi = kx[(long)b * N + i], kyi = ky[(long)b * N + i];
-    const cx<T> e = mu[b] * E[o], gx = Gx[o], gy = Gy[o];
-    const int n = 2 * N;
-    cx<T>* Ab = A + (long)b * n * n;
-    cx<T> a11 = e - kxi * gx, a12 = -(kxi * gy), a21 = -(kyi * gx), a22 = e - kyi * gy;
-    if (i == j) { a11 -= kyi * kyi; a22 -= kxi * kxi; a12 += kxi * kyi; a21 += kxi * kyi; }
-    Ab[(long)i * n + j] = a11;
-    Ab[(long)i * n + j + N] = a12;
-    Ab[(long)(i + N) * n + j] = a21;
-    Ab[(long)(i + N) * n + j + N] = a22;
-}
-template <class T>
-int build_a_t(hipStream_t s, const cx<T>* E, const cx<T>* Ei, const cx<T>* mu, const cx<T>* kx, const cx<T>* ky, int N, int batch, cx<T>* A, cx<T>* ws) {
-    const long NN = (long)N * N, bNN = (long)batch * NN;
-    const cx<T> one(T(1), T(0)), zero(T(0), T(0));
-    const dim3 g(cdiv_i(N, 256), N, batch), blk(256);
-    cx<T>*Sx = ws, *Gx = ws + bNN, *Gy = ws + 2 * bNN;
-    TRX_LAUNCH((scale_rows_kernel<T>), g, blk, 0, s, E, kx, N, Sx);
-    int rc = gemm<T>(s, TRX_OP_N, TRX_OP_N, N, N, N, one, Ei, N, NN, Sx, N, NN, zero, Gx, N, NN, batch); if (rc) return rc;
-    TRX_LAUNCH((scale_rows_kernel<T>), g, blk, 0, s, E, ky, N, Sx);
-    rc = gemm<T>(s, TRX_OP_N, TRX_OP_N, N, N, N, one, Ei, N, NN, Sx, N, NN, zero, Gy, N, NN, batch); if (rc) return rc;
-    TRX_LAUNCH((assemble_a_kernel<T>), g, blk, 0, s, E, (const cx<T>*)Gx, (const cx<T>*)Gy, mu, kx, ky, N, A);
-    TRX_CHECK_LAUNCH();
-    return TRX_OK;
-}
-
 }  // namespace
 }  // namespace trx
 
 using namespace trx;
-
-extern "C" int trx_build_pq(int dtype, const void* E, const void* Einv, const void* Mu, const void* Muinv, const void* kx,
-                            const void* ky, int N, int batch, void* P, void* Q, void* stream) {
-    if (!E || !Einv || !Mu || !Muinv || !kx || !ky || !P || !Q || N <= 0 || batch <= 0) return TRX_ERR_ARG;
-    hipStream_t s = trx::api_stream(stream);
-    if (dtype == TRX_C64) return build_pq_t<float>(s, E, Einv, Mu, Muinv, kx, ky, N, batch, P, Q);
-    if (dtype == TRX_C128) return build_pq_t<double>(s, E, Einv, Mu, Muinv, kx, ky, N, batch, P, Q);
-    return TRX_ERR_DTYPE;
-}
 
 extern "C" size_t trx_layer_smatrix_ws_bytes(int dtype, int N, int batch) {
     return (size_t)(dtype == TRX_C128 ? 16 : 8) * 6 * (size_t)batch * (2 * (size_t)N) * (2 * (size_t)N);
@@ -760,18 +672,4 @@ extern "C" int trx_redheffer_halfspace_columns(int dtype, int side, const void* 
                                                     piv, info, (cx<float>*)ws);
     return redheffer_halfspace_columns_t<double>(s, dtype, side, (const cx<double>*)bd, (const cx<double>* const*)S, block, cols, m, (cx<double>*)out, N, batch,
                                                  piv, info, (cx<double>*)ws);
-}
-
-extern "C" size_t trx_build_a_ws_bytes(int dtype, int N, int batch) {
-    return (size_t)(dtype == TRX_C128 ? 16 : 8) * 3 * (size_t)batch * N * N;
-}
-
-extern "C" int trx_build_a(int dtype, const void* E, const void* Einv, const void* mu, const void* kx, const void* ky, int N, int batch, void* A,
-                           void* ws, size_t ws_bytes, void* stream) {
-    if (!E || !Einv || !mu || !kx || !ky || !A || !ws || N <= 0 || batch <= 0) return TRX_ERR_ARG;
-    if (ws_bytes < trx_build_a_ws_bytes(dtype, N, batch)) return TRX_ERR_WORKSPACE;
-    hipStream_t s = trx::api_stream(stream);
-    if (dtype == TRX_C64) return build_a_t<float>(s, (const cx<float>*)E, (const cx<float>*)Einv, (const cx<float>*)mu, (const cx<float>*)kx, (const cx<float>*)ky, N, batch, (cx<float>*)A, (cx<float>*)ws);
-    if (dtype == TRX_C128) return build_a_t<double>(s, (const cx<double>*)E, (const cx<double>*)Einv, (const cx<double>*)mu, (const cx<double>*)kx, (const cx<double>*)ky, N, batch, (cx<double>*)A, (cx<double>*)ws);
-    return TRX_ERR_DTYPE;
 }

@@ -372,16 +372,6 @@ class Engine:
         return gA
 
     # -- a6 / a8 / a9 ----------------------------------------------------------------------------------
-    @_phase("assembly (convolution matrices, E^-1, A = PQ)")
-    def build_pq(self, E, Einv, M, Minv, kx, ky):
-        B, N, _ = E.shape
-        dt = E.dtype
-        P = torch.empty((B, 2 * N, 2 * N), dtype=dt, device=self.device)
-        Q = torch.empty_like(P)
-        self.lib.check(self.lib.build_pq(_CODE[dt], self._c(E).data_ptr(), self._c(Einv).data_ptr(), self._c(M).data_ptr(), self._c(Minv).data_ptr(),
-                                         self._c(kx).data_ptr(), self._c(ky).data_ptr(), N, B, P.data_ptr(), Q.data_ptr(), self.stream))
-        return P, Q
-
     @_phase("layer S-matrix (V = P^-1 W Kz, trx_layer_smatrix)")
     def hmodes(self, E, mu, kx, ky, W, kz):
         """V = P^-1 W diag(kz) for homogeneous mu [B] via the rank-N structure of P (include/trx.h: trx_hmodes)."""
@@ -497,67 +487,58 @@ class Engine:
         self._info(info, "redheffer_halfspace_columns")
         return out
 
+    # -- eigenproblem assembly (csrc/assembly.hip) --------------------------------------------------------
+    def _build_pq(self, entry, *ops):
+        """P, Q [B,2N,2N] from one of the trx_build_pq* entries; ops: its [B,N,N] matrices, then kx, ky [B,N], in the entry's order."""
+        ops = [self._c(t) for t in ops]
+        self._check(*ops)
+        B, N, _ = ops[0].shape
+        P = torch.empty((B, 2 * N, 2 * N), dtype=ops[0].dtype, device=self.device)
+        Q = torch.empty_like(P)
+        self.lib.check(entry(_CODE[P.dtype], *[t.data_ptr() for t in ops], N, B, P.data_ptr(), Q.data_ptr(), self.stream))
+        return P, Q
+
+    def _build_a(self, entry, ws_bytes, mats, mu, kx, ky):
+        """A = P Q [B,2N,2N] for homogeneous mu [B] from one of the trx_build_a* entries (workspace: its ws_bytes); mats: its [B,N,N] matrices."""
+        B, N, _ = mats[0].shape
+        dt = mats[0].dtype
+        A = torch.empty((B, 2 * N, 2 * N), dtype=dt, device=self.device)
+        nws = ws_bytes(_CODE[dt], N, B)
+        ws = self._ws(nws)
+        ops = [self._c(t) for t in (*mats, mu.to(dt), kx, ky)]
+        self._check(*ops)
+        self.lib.check(entry(_CODE[dt], *[t.data_ptr() for t in ops], N, B, A.data_ptr(), ws.data_ptr(), nws, self.stream))
+        return A
+
+    @_phase("assembly (convolution matrices, E^-1, A = PQ)")
+    def build_pq(self, E, Einv, M, Minv, kx, ky):
+        """P, Q of torcwa/rcwa.py:1226-1232 (Laurent's rule; include/trx.h: trx_build_pq)."""
+        return self._build_pq(self.lib.build_pq, E, Einv, M, Minv, kx, ky)
+
     @_phase("assembly (convolution matrices, E^-1, A = PQ)")
     def build_a(self, E, Einv, mu, kx, ky):
         """A = P Q for homogeneous mu [B] via the block structure (two N^3 GEMMs)."""
-        B, N, _ = E.shape
-        dt = E.dtype
-        A = torch.empty((B, 2 * N, 2 * N), dtype=dt, device=self.device)
-        nws = self.lib.build_a_ws_bytes(_CODE[dt], N, B)
-        ws = self._ws(nws)
-        self.lib.check(self.lib.build_a(_CODE[dt], self._c(E).data_ptr(), self._c(Einv).data_ptr(), self._c(mu.to(dt)).data_ptr(), self._c(kx).data_ptr(),
-                                        self._c(ky).data_ptr(), N, B, A.data_ptr(), ws.data_ptr(), nws, self.stream))
-        return A
+        return self._build_a(self.lib.build_a, self.lib.build_a_ws_bytes, (E, Einv), mu, kx, ky)
 
     @_phase("assembly (convolution matrices, E^-1, A = PQ)")
     def build_pq_aniso(self, Ex, Ey, Einv, Mx, My, Minv, kx, ky):
         """P, Q with per-component convolution matrices (Li's rule; include/trx.h: trx_build_pq_aniso)."""
-        B, N, _ = Ex.shape
-        dt = Ex.dtype
-        P = torch.empty((B, 2 * N, 2 * N), dtype=dt, device=self.device)
-        Q = torch.empty_like(P)
-        ops = [self._c(t) for t in (Ex, Ey, Einv, Mx, My, Minv, kx, ky)]
-        self._check(*ops)
-        self.lib.check(self.lib.build_pq_aniso(_CODE[dt], *[t.data_ptr() for t in ops], N, B, P.data_ptr(), Q.data_ptr(), self.stream))
-        return P, Q
+        return self._build_pq(self.lib.build_pq_aniso, Ex, Ey, Einv, Mx, My, Minv, kx, ky)
 
     @_phase("assembly (convolution matrices, E^-1, A = PQ)")
     def build_a_aniso(self, Ex, Ey, Einv, mu, kx, ky):
         """A = P Q for homogeneous mu [B] with per-component Ex, Ey (two N^3 GEMMs; include/trx.h: trx_build_a_aniso)."""
-        B, N, _ = Ex.shape
-        dt = Ex.dtype
-        A = torch.empty((B, 2 * N, 2 * N), dtype=dt, device=self.device)
-        nws = self.lib.build_a_aniso_ws_bytes(_CODE[dt], N, B)
-        ws = self._ws(nws)
-        ops = [self._c(t) for t in (Ex, Ey, Einv, mu.to(dt), kx, ky)]
-        self._check(*ops)
-        self.lib.check(self.lib.build_a_aniso(_CODE[dt], *[t.data_ptr() for t in ops], N, B, A.data_ptr(), ws.data_ptr(), nws, self.stream))
-        return A
+        return self._build_a(self.lib.build_a_aniso, self.lib.build_a_aniso_ws_bytes, (Ex, Ey, Einv), mu, kx, ky)
 
     @_phase("assembly (convolution matrices, E^-1, A = PQ)")
     def build_pq_tensor(self, Exx, Exy, Eyy, Einv, M, Minv, kx, ky):
         """P, Q with the in-plane permittivity tensor (normal-vector rule; include/trx.h: trx_build_pq_tensor)."""
-        B, N, _ = Exx.shape
-        dt = Exx.dtype
-        P = torch.empty((B, 2 * N, 2 * N), dtype=dt, device=self.device)
-        Q = torch.empty_like(P)
-        ops = [self._c(t) for t in (Exx, Exy, Eyy, Einv, M, Minv, kx, ky)]
-        self._check(*ops)
-        self.lib.check(self.lib.build_pq_tensor(_CODE[dt], *[t.data_ptr() for t in ops], N, B, P.data_ptr(), Q.data_ptr(), self.stream))
-        return P, Q
+        return self._build_pq(self.lib.build_pq_tensor, Exx, Exy, Eyy, Einv, M, Minv, kx, ky)
 
     @_phase("assembly (convolution matrices, E^-1, A = PQ)")
     def build_a_tensor(self, Exx, Exy, Eyy, Einv, mu, kx, ky):
         """A = P Q for homogeneous mu [B] with the in-plane tensor (one N x 2N GEMM; include/trx.h: trx_build_a_tensor)."""
-        B, N, _ = Exx.shape
-        dt = Exx.dtype
-        A = torch.empty((B, 2 * N, 2 * N), dtype=dt, device=self.device)
-        nws = self.lib.build_a_tensor_ws_bytes(_CODE[dt], N, B)
-        ws = self._ws(nws)
-        ops = [self._c(t) for t in (Exx, Exy, Eyy, Einv, mu.to(dt), kx, ky)]
-        self._check(*ops)
-        self.lib.check(self.lib.build_a_tensor(_CODE[dt], *[t.data_ptr() for t in ops], N, B, A.data_ptr(), ws.data_ptr(), nws, self.stream))
-        return A
+        return self._build_a(self.lib.build_a_tensor, self.lib.build_a_tensor_ws_bytes, (Exx, Exy, Eyy, Einv), mu, kx, ky)
 
     # -- power flux ------------------------------------------------------------------------------------
     @_phase("power flux (trx_matvec, trx_layer_flux)")
