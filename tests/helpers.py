@@ -143,3 +143,7 @@ def lu_interchanges(A):
         A[k + 1:, k] /= A[k, k]
         A[k + 1:, k + 1:] -= np.outer(A[k + 1:, k], A[k, k + 1:])
     return cnt
+
+
+from tests.eig_reference import eig_hp  # noqa: E402,F401  (the eigen-reference beyond complex128, next to solve_hp; its own module so that
+#                                                             tests/test_eig_blocks.py needs nothing of this file beyond crandn)

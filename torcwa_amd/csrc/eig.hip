@@ -259,7 +259,9 @@ int eig_t(hipStream_t s, void* A, void* w, void* V, int n, int batch, int* info,
             RefineBuffers<T> R;
             // Z (dead A32 / Z32 of the fp32 solve by now) takes the LU of the fp32 start and E; X takes the fp64 residual.  V32 lies at the END of
             // the pool (behind Z, inside X and the spill): it is copied / converted before X is first written.
-            R.Rb = B.X; R.LU32 = (cx<float>*)B.Z; R.E32 = R.LU32 + Bn * N * N; R.d0 = B.r_d0; R.piv = B.r_piv; R.linfo = B.r_linfo; R.flags = B.r_flags;
+            // E32 doubles as the fp64 product buffer Pw of eig_refine: it starts on a 16-byte boundary (batch * n * n odd leaves LU32's end 8 bytes
+            // off one; Z's rounding to 256 bytes then has at least 16 bytes to spare, and Pw is shorter than E by 8 * batch * n bytes)
+            R.Rb = B.X; R.LU32 = (cx<float>*)B.Z; R.E32 = R.LU32 + ((Bn * N * N + 1) & ~(size_t)1); R.d0 = B.r_d0; R.piv = B.r_piv; R.linfo = B.r_linfo; R.flags = B.r_flags;
             R.eoff = B.r_eoff; R.lmax = B.r_lmax; R.scan_part = B.r_scan; R.partner = B.r_partner; R.clus = B.r_clus; R.edges = B.r_edges; R.ecount = B.r_ecount; R.tab = B.r_tab;
             int any = 0;
             std::vector<int> bad(batch, 0);
