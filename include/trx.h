@@ -378,13 +378,32 @@ int trx_modal_overlap(int dtype, const void* M, const void* cplus, const void* c
  * per group): W[:, off[k]:off[k+1]] = T_k W_k, lam = the block eigenvalues in block order.  T is unitary, so the columns of W keep the unit
  * 2-norm of trx_eig's geev convention and A W = W diag(lam) holds in the original basis.  W is zero-filled first (rows a block does not reach),
  * then every element has one writer: 2 n^2 written, sum_k n_k^2 read.  No workspace.
- * Both: stream-ordered, no host synchronisation; complex64 and complex128; n^2 < 2^31, batch <= 65535, else TRX_ERR_ARG; batch = 0 returns
- * TRX_OK without touching any buffer.  Element alignment suffices for every buffer but ws. */
+ * Adjoints, in PyTorch's complex convention (a linear map Y = L(X) has gX = L^H(gY)); they make the folded eigenproblem differentiable:
+ * trx_sym_fold_backward: gA [batch,n,n] = sum_k T_k gB_k T_k^H from the packed block gradients gblocks (the packing of trx_sym_fold's output).
+ * resid carries no gradient.  Only the diagonal blocks of T^H A T reach the output of trx_sym_fold, so gA is the gradient of the
+ * mirror-constrained problem: it commutes with the mirrors whatever gblocks holds.  The kernel reads the ROW plan, built by the caller like
+ * the plan itself:
+ *   ridx [n,4] int32   slot k: the column of block k (a column index of T, in off[k] .. off[k+1]-1) whose support holds row r
+ *   rwt  [n,4] `dtype` T's entry there, 0 if block k has no such column (and for slots k >= nblk); ridx of such a slot: any value
+ * (a row lies in at most one column per block because the supports inside a block are disjoint), so that
+ *   gA[r,c] = sum_k rwt[r,k] gB_k[ridx[r,k] - off[k], ridx[c,k] - off[k]] conj(rwt[c,k]):
+ * a gather with one writer per element; no zero fill, no workspace, no atomics.  Indices are clamped into their block.  A malformed off fills
+ * gA with NaN.  Traffic model (elements per matrix): n^2 written, at most one element of gB_k read per element and block: (1 + nblk) n^2.
+ * trx_sym_unfold_backward: gWk (packed) and glamk (packed) from gW [batch,n,n] and glam [batch,n]: gW_k = T_k^H gW[:, off[k]:off[k+1]] (row j a
+ * combination of the at most four rows idx[off[k]+j][q] of gW with conj(wt)), glam_k = glam[off[k]:off[k+1]]; the layout trx_sym_unfold reads.
+ * Every element of gWk and glamk is written, the inputs are not modified.  A malformed off leaves gWk alone (its packing is not defined) and
+ * fills glamk, batch n elements whatever the blocks, with NaN.  Traffic model: n^2 read, sum_k n_k^2 written: (1 + 1 / nblk) n^2.  No workspace.
+ * All four: stream-ordered, no host synchronisation, deterministic; complex64 and complex128; n^2 < 2^31, batch <= 65535, 1 <= nblk <= 4, else
+ * TRX_ERR_ARG; batch = 0 returns TRX_OK without touching any buffer.  Element alignment suffices for every buffer but ws. */
 size_t trx_sym_fold_ws_bytes(int dtype, int n, int batch);
 int trx_sym_fold(int dtype, const void* A, int n, int batch, const int* idx, const void* wt, const int* off, int nblk, void* blocks, double* resid,
                  void* ws, size_t ws_bytes, void* stream);
 int trx_sym_unfold(int dtype, const void* Wk, const void* lamk, int n, int batch, const int* idx, const void* wt, const int* off, int nblk, void* W,
                    void* lam, void* stream);
+int trx_sym_fold_backward(int dtype, const void* gblocks, int n, int batch, const int* ridx, const void* rwt, const int* off, int nblk, void* gA,
+                          void* stream);
+int trx_sym_unfold_backward(int dtype, const void* gW, const void* glam, int n, int batch, const int* idx, const void* wt, const int* off, int nblk,
+                            void* gWk, void* glamk, void* stream);
 
 /* ---- thickness sweeps that reuse a layer's modes (no reference counterpart; what modal solvers offer as a layer-thickness scan) ----------------
  * The modes W, kz, V of a layer do not depend on its thickness d, only the diagonal phase X = exp(i omega kz d) does.  With F = Vf^-1 V (the
@@ -439,7 +458,8 @@ int trx_thickness_columns(int dtype, const void* rhoL, const void* rhoR, const v
  * milliseconds of the timed launches, flops of ALL launches, bytes of ALL launches} (the last two are exact sums, not samples).  Tags: 0 gemm N,N; 1 gemm other ops; 2 QR prepare (AED);
  * 3 QR off-window update; 4 QR window chase; 5 Hessenberg gemv; 6 Hessenberg reflector column; 7 LU panel; 8 - 15 see trx_prof_tag_name;
  * 16 trx_sym_fold (both passes); 17 trx_sym_unfold (zero fill and scatter); 18 trx_thickness_prepare (whole call); 19 - 21 the stages of
- * trx_thickness_columns, one event pair per call each: 19 K assembly and its GEMMs, 20 LU of K and the column solve, 21 amplitudes and read-out. */
+ * trx_thickness_columns, one event pair per call each: 19 K assembly and its GEMMs, 20 LU of K and the column solve, 21 amplitudes and read-out;
+ * 22 trx_sym_fold_backward; 23 trx_sym_unfold_backward. */
 int trx_prof_enable(int on);
 int trx_prof_reset(void);
 int trx_prof_get(int tag, double* out);

@@ -196,3 +196,35 @@ class SolveFn(torch.autograd.Function):
         gB = eng.solve(AH, G.contiguous())                                    # A^-H G
         gA = -eng.gemm(gB, X, opB=2) if ctx.needs_input_grad[0] else None     # - gB X^H
         return gA, gB, None
+
+
+class SymFoldFn(torch.autograd.Function):
+    """(blocks of T^H A T per size group ..., resid) = engine.sym_fold(A, plan); resid is not differentiable.
+    backward: gA = sum_k T_k gB_k T_k^H (trx_sym_fold_backward)."""
+
+    @staticmethod
+    def forward(ctx, A, plan, engine):
+        ctx.engine, ctx.plan = engine, plan
+        blocks, resid = engine.sym_fold(A, plan)
+        ctx.mark_non_differentiable(resid)
+        return (*blocks, resid)
+
+    @staticmethod
+    def backward(ctx, *grads):
+        return ctx.engine.sym_fold_backward([g.contiguous() for g in grads[:-1]], ctx.plan), None, None
+
+
+class SymUnfoldFn(torch.autograd.Function):
+    """(lam, W) = engine.sym_unfold(Wk, lamk, plan) for per-group lists, passed flat: SymUnfoldFn.apply(plan, engine, *Wk, *lamk).
+    backward: gW_k = T_k^H gW[:, block k], glam_k = the slices of glam (trx_sym_unfold_backward)."""
+
+    @staticmethod
+    def forward(ctx, plan, engine, *parts):
+        ctx.engine, ctx.plan = engine, plan
+        g = len(plan.groups)
+        return engine.sym_unfold(list(parts[:g]), list(parts[g:]), plan)
+
+    @staticmethod
+    def backward(ctx, glam, gW):
+        gWk, glamk = ctx.engine.sym_unfold_backward(gW, glam, ctx.plan)
+        return (None, None, *gWk, *glamk)

@@ -94,7 +94,7 @@ class BatchedRCWA(FluxMixin, VolumeMixin):
     def __init__(self, freq, order, L, *, batch=None, dtype=torch.complex64, device=None, stable_eig_grad=True,
                  avoid_Pinv_instability=False, max_Pinv_instability=0.005, precision="high", engine=None,
                  keep_coupling=True, fold_layers=False, eig_route="auto", route_hint=None, fourier_rule="laurent", nv_sigma=NV_SIGMA_DEFAULT,
-                 symmetry=None, symmetry_tol=1e-6):
+                 symmetry=None, symmetry_tol=1e-6, symmetry_grad=False):
         check_fourier_rule(fourier_rule)
         # symmetry (extension): None | "x" | "y" | "xy" -- the caller states that every patterned layer is invariant under x -> -x (y -> -y) about
         # a plane and that kx0 = 0 (ky0 = 0) at every sweep point.  A = P Q of such a layer is then folded into 2 / 4 independent eigenproblems
@@ -106,6 +106,13 @@ class BatchedRCWA(FluxMixin, VolumeMixin):
         self.symmetry_tol = float(symmetry_tol)
         self.symmetry_residual = []      # per layer: resid [B] of trx_sym_fold (the discarded part of T^H A T relative to max |A|), or None
         self._sym_plans = {}
+        # symmetry_grad=True (opt-in): a differentiable stack folds its eigenproblems too (SymFoldFn -> Eig per block size -> SymUnfoldFn).
+        # The fold drops the part of A outside the diagonal blocks, so the eigen-part of the gradient is the one of the mirror-constrained
+        # problem: gradients with respect to symmetric parameters (radii, widths, thicknesses, a symmetrised density) and the mirror average of
+        # a per-pixel gradient are those of the unfolded path, a raw per-pixel gradient is not.
+        self.symmetry_grad = bool(symmetry_grad)
+        if self.symmetry_grad and symmetry is None:
+            raise ValueError('symmetry_grad=True needs symmetry="x" | "y" | "xy"')
         # fourier_rule="li" needs the rectangular order box on a rectangular lattice (ValueError otherwise, see the order / lattice below).
         # fourier_rule="li": Li's inverse rule for the x / y components of D in every patterned layer (Ex, Ey convolution matrices,
         # include/trx.h trx_convmat_li); Ez / Hz keep Laurent's matrices (E^-1 in P, trx_hmodes, eps_conv).  "laurent": the reference's rule.
@@ -318,9 +325,10 @@ class BatchedRCWA(FluxMixin, VolumeMixin):
             raise ValueError("swept=True is not available on a differentiable stack (a tensor of this layer or another one requires grad): "
                              "the adjoint of the thickness sweep is not implemented")
         if self.symmetry is not None:
-            if self._diff:
+            if self._diff and not self.symmetry_grad:
                 raise ValueError("symmetry= is not available on a differentiable stack (a tensor of this layer or an earlier one requires grad): "
-                                 "the adjoint of the folded eigenproblem is not implemented")
+                                 "the adjoint of the folded eigenproblem is not implemented for a raw per-pixel gradient; symmetry_grad=True "
+                                 "opts in to the gradient of the mirror-constrained problem")
             if normal_field is not None:
                 raise ValueError("symmetry= cannot be combined with add_layer(normal_field=...): a caller-supplied field is not checked for the mirror; "
                                  "let the field be derived from the grid")
@@ -373,7 +381,11 @@ class BatchedRCWA(FluxMixin, VolumeMixin):
                 A = ag.GemmFn.apply(P, Q, eng)
                 # stable_eig_grad=False is the reference's plain torch.linalg.eig branch (rcwa.py:1238): its backward is never
                 # broadened.  The choice is bound to this graph node (not to the process-global at backward time).
-                lam, W = Eig.apply(A) if self.stable_eig_grad else Eig.apply(A, Eig.UNBROADENED)
+                eig = Eig.apply if self.stable_eig_grad else (lambda M: Eig.apply(M, Eig.UNBROADENED))
+                if plan is None:
+                    lam, W = eig(A)
+                else:
+                    lam, W, resid = self._eig_folded_diff(A, plan, eig)
             else:
                 A = self._a(fac, P, Q)
                 # the factorised medium dies here, before the eigensolver's peak: E, M live on in eps_conv / mu_conv, Li's / the
@@ -467,7 +479,7 @@ class BatchedRCWA(FluxMixin, VolumeMixin):
             M, Minv, mu_s = conv(mu, mu_h)
         plan = None
         if self.symmetry is not None and not (eps_h and mu_h):          # before any heavy work: a grid without the mirror raises here
-            plan = self._sym_plan([torch.as_tensor(v, device=self._device) for v, h in ((eps, eps_h), (mu, mu_h)) if not h])
+            plan = self._sym_plan([torch.as_tensor(v, device=self._device).detach() for v, h in ((eps, eps_h), (mu, mu_h)) if not h])
         exx, exy, eyy, mx, my = E, None, E, M, M
         if self.fourier_rule == "li" and not (eps_h and mu_h):
             exx, eyy = conv_li(eps, eps_h, E)
@@ -785,6 +797,15 @@ class BatchedRCWA(FluxMixin, VolumeMixin):
                 self._eig_call(Bk, refine_steps=refine_steps, out=(lk, wk))
         del blocks
         lam, W = eng.sym_unfold(Wp, lp, plan)
+        return lam, W, resid
+
+    def _eig_folded_diff(self, A, plan, eig):
+        """_eig_folded for a differentiable A: every step is an autograd.Function over the HIP kernels (trx_sym_fold / _backward, Eig per
+        distinct block size, trx_sym_unfold / _backward).  resid carries no gradient."""
+        eng = self.engine
+        *blocks, resid = ag.SymFoldFn.apply(A, plan, eng)
+        pairs = [eig(Bk) if Bk.shape[-1] > 0 else (Bk.new_empty(Bk.shape[:2]), Bk) for Bk in blocks]
+        lam, W = ag.SymUnfoldFn.apply(plan, eng, *[p[1] for p in pairs], *[p[0] for p in pairs])
         return lam, W, resid
 
     def _is_homogeneous(self, v):

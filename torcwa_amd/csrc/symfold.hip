@@ -15,6 +15,18 @@
 // C (2 n^2) and writes sum_k n_k^2 ~ n^2 / nblk: (nblk + 2 + 1 / nblk) n^2 = 4.5 n^2 / 6.25 n^2; unfold writes W twice (zero fill, n^2 each) and
 // reads sum_k n_k^2: (2 + 1 / nblk) n^2.  Both are far below one GEMM of the same size.  Maxima are exact and order-independent;
 // per workgroup one partial goes to the workspace and a second kernel combines them: deterministic, no atomics.
+//
+// Adjoints (trx_sym_fold_backward, trx_sym_unfold_backward; PyTorch's convention: Y = L(X) has gX = L^H(gY)).
+//   fold backward    gA = sum_k T_k gB_k T_k^H.  A row r of the original basis lies in at most one column of T per block, so with the ROW plan
+//                    (ridx[r][k], rwt[r][k]: that column of block k and T's entry, weight 0 if there is none) this is a gather with one writer
+//                    per element: gA[r, c] = sum_k rwt[r][k] gB_k[ridx[r][k] - off[k], ridx[c][k] - off[k]] conj(rwt[c][k]).  The lanes of a wave
+//                    walk c: the gathers of one row stay inside one row of gB_k, the writes are coalesced.  No zero fill, workspace or atomics.
+//   unfold backward  gW_k = T_k^H gW[:, off[k]:off[k+1]]: row j of gW_k is a combination of the at most four rows idx[off[k] + j][q] of gW with
+//                    conj(wt), read and written along the rows; glam_k is the matching slice of glam.
+// Traffic model per matrix: fold backward writes n^2, reads one element of gB_k per block whose weights are both non-zero (at most nblk n^2; the
+// distinct elements are sum_k n_k^2 ~ n^2 / nblk and the re-reads of an orbit fall in the same rows) and 2 n plan rows per SF_ROWS rows:
+// counted as (1 + nblk) n^2.  unfold backward reads every element of gW once (n^2: the supports of the columns of one block are disjoint) and
+// writes sum_k n_k^2 ~ n^2 / nblk: (1 + 1 / nblk) n^2.
 #include "common.hpp"
 #include "prof.hpp"
 
@@ -216,6 +228,90 @@ __global__ __launch_bounds__(SF_THREADS) void sym_unfold_kernel(const cx<T>* __r
     }
 }
 
+// gA = sum_k T_k gB_k T_k^H from the row plan.  grid (ceil(n / SF_ROWS), batch); a malformed off fills gA with NaN.
+template <class T>
+__global__ __launch_bounds__(SF_THREADS) void sym_fold_bwd_kernel(const cx<T>* __restrict__ gB, const int* __restrict__ ridx, const cx<T>* __restrict__ rwt,
+                                                                  const int* __restrict__ off, int nblk, int n, int batch, cx<T>* __restrict__ gA) {
+    const int tid = threadIdx.x, b = blockIdx.y, r0 = blockIdx.x * SF_ROWS;
+    const SymLayout L = sym_layout(off, nblk, n, batch);
+    cx<T>* Ab = gA + (long)b * n * n;
+    const int rows = n - r0 < SF_ROWS ? n - r0 : SF_ROWS;
+    if (!L.ok) {
+        const T bad = (T)__builtin_nan("");
+        for (int rr = 0; rr < rows; ++rr)
+            for (int c = tid; c < n; c += SF_THREADS) Ab[(long)(r0 + rr) * n + c] = cx<T>(bad, bad);
+        return;
+    }
+    for (int c = tid; c < n; c += SF_THREADS) {
+        int lc[SF_MAXBLK];
+        cx<T> wc[SF_MAXBLK];
+#pragma unroll
+        for (int k = 0; k < SF_MAXBLK; ++k) {
+            const int s = L.off[k + 1] - L.off[k];
+            wc[k] = cx<T>(T(0), T(0));
+            lc[k] = 0;
+            if (k < nblk && s > 0) {
+                wc[k] = conj(rwt[c * 4 + k]);
+                lc[k] = clamp_row(ridx[c * 4 + k] - L.off[k], s);
+            }
+        }
+        for (int rr = 0; rr < rows; ++rr) {
+            const int r = r0 + rr;
+            cx<T> acc(T(0), T(0));
+#pragma unroll
+            for (int k = 0; k < SF_MAXBLK; ++k) {
+                const int s = L.off[k + 1] - L.off[k];
+                if (k >= nblk || s <= 0) continue;
+                const cx<T> wr = rwt[r * 4 + k];                                        // wave-uniform
+                if (nonzero(wr) && nonzero(wc[k])) {
+                    const int lr = clamp_row(ridx[r * 4 + k] - L.off[k], s);
+                    const cx<T> g = gB[L.base2[k] + (long)b * s * s + (long)lr * s + lc[k]];
+                    cfma(acc, wr * g, wc[k]);
+                }
+            }
+            Ab[(long)r * n + c] = acc;
+        }
+    }
+}
+
+// gWk[j, c] = sum_q conj(wt[J][q]) gW[idx[J][q], off[k] + c] for column J = off[k] + j of T; glamk[j] = glam[J].  grid (ceil(n / SF_ROWS), batch).
+// A malformed off: the packing of gWk is not defined, so it is left alone and glamk (batch n elements whatever the blocks) is filled with NaN.
+template <class T>
+__global__ __launch_bounds__(SF_THREADS) void sym_unfold_bwd_kernel(const cx<T>* __restrict__ gW, const cx<T>* __restrict__ glam, const int* __restrict__ idx,
+                                                                    const cx<T>* __restrict__ wt, const int* __restrict__ off, int nblk, int n, int batch,
+                                                                    cx<T>* __restrict__ gWk, cx<T>* __restrict__ glamk) {
+    const int tid = threadIdx.x, b = blockIdx.y, J0 = blockIdx.x * SF_ROWS;
+    const SymLayout L = sym_layout(off, nblk, n, batch);
+    if (!L.ok) {
+        const T bad = (T)__builtin_nan("");
+        if (tid < SF_ROWS && J0 + tid < n) glamk[(long)b * n + J0 + tid] = cx<T>(bad, bad);
+        return;
+    }
+    const cx<T>* Gb = gW + (long)b * n * n;
+    for (int rr = 0; rr < SF_ROWS && J0 + rr < n; ++rr) {
+        const int J = J0 + rr;
+        const int k = block_of(L, nblk, J);
+        const long s = L.off[k + 1] - L.off[k];
+        const int j = J - L.off[k];
+        cx<T>* dst = gWk + L.base2[k] + (long)b * s * s + (long)j * s;
+        int rw[4];
+        cx<T> w[4];
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            rw[q] = clamp_row(idx[J * 4 + q], n);
+            w[q] = conj(wt[J * 4 + q]);
+        }
+        for (int c = tid; c < (int)s; c += SF_THREADS) {
+            cx<T> acc(T(0), T(0));
+#pragma unroll
+            for (int q = 0; q < 4; ++q)
+                if (nonzero(w[q])) cfma(acc, w[q], Gb[(long)rw[q] * n + L.off[k] + c]);     // wave-uniform
+            dst[c] = acc;
+        }
+        if (tid == 0) glamk[L.base1[k] + (long)b * s + j] = glam[(long)b * n + J];
+    }
+}
+
 size_t part_bytes(int n, int batch) { return sizeof(double) * 2 * (size_t)cdiv_i(n, SF_ROWS) * (size_t)batch; }
 
 template <class T>
@@ -244,6 +340,26 @@ int sym_unfold_t(hipStream_t st, const cx<T>* Wk, const cx<T>* lamk, int n, int 
     ProfScope prof(PROF_SYM_UNFOLD, st, 0.0, sizeof(cx<T>) * (2.0 + 1.0 / (nblk > 0 ? nblk : 1)) * nn);
     if (hipMemsetAsync(W, 0, sizeof(cx<T>) * (size_t)n * n * batch, st) != hipSuccess) return TRX_ERR_LAUNCH;
     TRX_LAUNCH((sym_unfold_kernel<T>), dim3(cdiv_i(n, SF_ROWS), batch), dim3(SF_THREADS), 0, st, Wk, lamk, idx, wt, off, nblk, n, batch, W, lam);
+    TRX_CHECK_LAUNCH();
+    return TRX_OK;
+}
+
+template <class T>
+int sym_fold_bwd_t(hipStream_t st, const cx<T>* gB, int n, int batch, const int* ridx, const cx<T>* rwt, const int* off, int nblk, cx<T>* gA) {
+    const double nn = (double)n * n * batch;
+    ProfScope prof(PROF_SYM_FOLD_BWD, st, 8.0 * 2.0 * nblk * nn, sizeof(cx<T>) * (1.0 + nblk) * nn);
+    TRX_LAUNCH((sym_fold_bwd_kernel<T>), dim3(cdiv_i(n, SF_ROWS), batch), dim3(SF_THREADS), 0, st, gB, ridx, rwt, off, nblk, n, batch, gA);
+    TRX_CHECK_LAUNCH();
+    return TRX_OK;
+}
+
+template <class T>
+int sym_unfold_bwd_t(hipStream_t st, const cx<T>* gW, const cx<T>* glam, int n, int batch, const int* idx, const cx<T>* wt, const int* off, int nblk,
+                     cx<T>* gWk, cx<T>* glamk) {
+    const double nn = (double)n * n * batch;
+    ProfScope prof(PROF_SYM_UNFOLD_BWD, st, 8.0 * nn, sizeof(cx<T>) * (1.0 + 1.0 / nblk) * nn);
+    TRX_LAUNCH((sym_unfold_bwd_kernel<T>), dim3(cdiv_i(n, SF_ROWS), batch), dim3(SF_THREADS), 0, st, gW, glam, idx, wt, off, nblk, n, batch, gWk,
+               glamk);
     TRX_CHECK_LAUNCH();
     return TRX_OK;
 }
@@ -289,4 +405,30 @@ extern "C" int trx_sym_unfold(int dtype, const void* Wk, const void* lamk, int n
                                    (cx<float>*)lam);
     return sym_unfold_t<double>(st, (const cx<double>*)Wk, (const cx<double>*)lamk, n, batch, idx, (const cx<double>*)wt, off, nblk, (cx<double>*)W,
                                 (cx<double>*)lam);
+}
+
+extern "C" int trx_sym_fold_backward(int dtype, const void* gblocks, int n, int batch, const int* ridx, const void* rwt, const int* off, int nblk,
+                                     void* gA, void* stream) {
+    const int rc = check_common(dtype, n, batch, nblk);
+    if (rc != TRX_OK) return rc;
+    if (batch == 0) return TRX_OK;
+    if (!gblocks || !ridx || !rwt || !off || !gA) return TRX_ERR_ARG;
+    hipStream_t st = trx::api_stream(stream);
+    if (dtype == TRX_C64)
+        return sym_fold_bwd_t<float>(st, (const cx<float>*)gblocks, n, batch, ridx, (const cx<float>*)rwt, off, nblk, (cx<float>*)gA);
+    return sym_fold_bwd_t<double>(st, (const cx<double>*)gblocks, n, batch, ridx, (const cx<double>*)rwt, off, nblk, (cx<double>*)gA);
+}
+
+extern "C" int trx_sym_unfold_backward(int dtype, const void* gW, const void* glam, int n, int batch, const int* idx, const void* wt, const int* off,
+                                       int nblk, void* gWk, void* glamk, void* stream) {
+    const int rc = check_common(dtype, n, batch, nblk);
+    if (rc != TRX_OK) return rc;
+    if (batch == 0) return TRX_OK;
+    if (!gW || !glam || !idx || !wt || !off || !gWk || !glamk) return TRX_ERR_ARG;
+    hipStream_t st = trx::api_stream(stream);
+    if (dtype == TRX_C64)
+        return sym_unfold_bwd_t<float>(st, (const cx<float>*)gW, (const cx<float>*)glam, n, batch, idx, (const cx<float>*)wt, off, nblk,
+                                       (cx<float>*)gWk, (cx<float>*)glamk);
+    return sym_unfold_bwd_t<double>(st, (const cx<double>*)gW, (const cx<double>*)glam, n, batch, idx, (const cx<double>*)wt, off, nblk,
+                                    (cx<double>*)gWk, (cx<double>*)glamk);
 }

@@ -752,6 +752,50 @@ class Engine:
                                            W.data_ptr(), lam.data_ptr(), self.stream))
         return lam, W
 
+    @_phase("symmetry fold backward (trx_sym_fold_backward)")
+    def sym_fold_backward(self, gblocks, plan):
+        """gA [B,n,n] = sum_k T_k gB_k T_k^H (include/trx.h: trx_sym_fold_backward), the adjoint of sym_fold.  gblocks: the flat packed buffer,
+        or a list with one [g * B, s, s] tensor per group of plan.groups (packed here)."""
+        n = plan.n
+        if torch.is_tensor(gblocks):
+            self._check(gblocks)
+            Gp = self._c(gblocks)
+            if Gp.dim() != 1:
+                raise ValueError("sym_fold_backward: a packed gblocks must be the flat buffer")
+        else:
+            self._check(*gblocks)
+            for (s, ks), g in zip(plan.groups, gblocks):
+                if g.dim() != 3 or tuple(g.shape[1:]) != (s, s) or g.shape[0] % len(ks):
+                    raise ValueError(f"sym_fold_backward: group of {len(ks)} blocks of size {s} needs [{len(ks)} B, {s}, {s}], got {list(g.shape)}")
+            Gp = torch.cat([g.reshape(-1) for g in gblocks])
+        tot = sum(s * s for s in plan.sizes)
+        B = Gp.numel() // tot
+        if Gp.numel() != B * tot:
+            raise ValueError(f"sym_fold_backward: {Gp.numel()} elements are no multiple of the plan's {tot} per matrix")
+        dt = Gp.dtype
+        _, _, off = plan.device(self.device, dt)
+        ridx, rwt = plan.rows(self.device, dt)
+        gA = torch.empty((B, n, n), dtype=dt, device=self.device)
+        self.lib.check(self.lib.sym_fold_backward(_CODE[dt], Gp.data_ptr(), n, B, ridx.data_ptr(), rwt.data_ptr(), off.data_ptr(), plan.nblk,
+                                                  gA.data_ptr(), self.stream))
+        return gA
+
+    @_phase("symmetry unfold backward (trx_sym_unfold_backward)")
+    def sym_unfold_backward(self, gW, glam, plan):
+        """(gWk, glamk): the adjoint of sym_unfold (include/trx.h: trx_sym_unfold_backward), gW_k = T_k^H gW[:, block k] and the slices of glam,
+        as lists with one [g * B, s, s] / [g * B, s] tensor per group of plan.groups (views of two packed buffers)."""
+        gW, glam = self._c(gW), self._c(glam)
+        self._check(gW, glam)
+        B, n, _ = gW.shape
+        if n != plan.n or tuple(glam.shape) != (B, n):
+            raise ValueError(f"sym_unfold_backward: gW {list(gW.shape)} / glam {list(glam.shape)} do not fit the plan's n = {plan.n}")
+        dt = gW.dtype
+        idx, wt, off = plan.device(self.device, dt)
+        Wp, lp, Wk, lamk = self.sym_packed(plan, B, dt)
+        self.lib.check(self.lib.sym_unfold_backward(_CODE[dt], gW.data_ptr(), glam.data_ptr(), n, B, idx.data_ptr(), wt.data_ptr(), off.data_ptr(),
+                                                    plan.nblk, Wp.data_ptr(), lp.data_ptr(), self.stream))
+        return Wk, lamk
+
 
 _default = None
 

@@ -49,6 +49,7 @@ class SymPlan:
             else:
                 self.groups.append((s, [k]))
         self._dev = {}
+        self._rows, self._rows_dev = None, {}
 
     def device(self, device, dtype):
         """(idx, wt, off) tensors on `device`, wt in `dtype`."""
@@ -57,6 +58,31 @@ class SymPlan:
             self._dev[key] = (torch.as_tensor(self.idx, device=device).contiguous(), torch.as_tensor(self.wt, device=device).to(dtype).contiguous(),
                               torch.as_tensor(np.asarray(self.off, dtype=np.int32), device=device).contiguous())
         return self._dev[key]
+
+    def rows(self, device=None, dtype=None):
+        """The row plan trx_sym_fold_backward reads: (ridx [n,4] int32, rwt [n,4]); slot k of row r names the column of block k whose support
+        holds r and T's entry there (weight 0, index off[k], if block k has none).  Without arguments the numpy arrays (rwt complex128), else
+        tensors on `device` with rwt in `dtype`, cached like device()."""
+        if self._rows is None:
+            ridx = np.repeat(np.asarray(self.off[:-1], dtype=np.int32)[None, :], self.n, axis=0)
+            ridx = np.concatenate([ridx, np.zeros((self.n, 4 - self.nblk), dtype=np.int32)], axis=1)
+            rwt = np.zeros((self.n, 4), dtype=np.complex128)
+            for k in range(self.nblk):
+                for j in range(self.off[k], self.off[k + 1]):
+                    for q in range(4):
+                        if self.wt[j, q] != 0:
+                            r = self.idx[j, q]
+                            if rwt[r, k] != 0:
+                                raise ValueError(f"SymPlan: row {r} lies in two columns of block {k}; the supports inside a block must be disjoint")
+                            ridx[r, k], rwt[r, k] = j, self.wt[j, q]
+            self._rows = (np.ascontiguousarray(ridx), rwt)
+        if device is None:
+            return self._rows
+        key = (str(device), dtype)
+        if key not in self._rows_dev:
+            self._rows_dev[key] = (torch.as_tensor(self._rows[0], device=device).contiguous(),
+                                   torch.as_tensor(self._rows[1], device=device).to(dtype).contiguous())
+        return self._rows_dev[key]
 
     def dense(self, dtype=np.clongdouble):
         """T as a dense [n, n] numpy array (tests, diagnostics)."""
