@@ -393,8 +393,22 @@ int trx_modal_overlap(int dtype, const void* M, const void* cplus, const void* c
  * combination of the at most four rows idx[off[k]+j][q] of gW with conj(wt)), glam_k = glam[off[k]:off[k+1]]; the layout trx_sym_unfold reads.
  * Every element of gWk and glamk is written, the inputs are not modified.  A malformed off leaves gWk alone (its packing is not defined) and
  * fills glamk, batch n elements whatever the blocks, with NaN.  Traffic model: n^2 read, sum_k n_k^2 written: (1 + 1 / nblk) n^2.  No workspace.
- * All four: stream-ordered, no host synchronisation, deterministic; complex64 and complex128; n^2 < 2^31, batch <= 65535, 1 <= nblk <= 4, else
- * TRX_ERR_ARG; batch = 0 returns TRX_OK without touching any buffer.  Element alignment suffices for every buffer but ws. */
+ * Sector folds: one pair of blocks of T^H M T for any M, not only one that commutes with the mirrors.  E -> E operators (A, the blocks of a
+ * layer S-matrix, of Sin / Sout) are block diagonal in T; E -> H and H -> E operators (Q, Vf; P, Vf^-1) connect block k with the opposite
+ * block only (H is a pseudovector), k' = nblk - 1 - k, which has the size of block k.
+ * trx_sym_fold_pair: out [batch,n_kl,n_kr] = T_kl^H M T_kr for M [batch,n,n] (not modified), 0 <= kl, kr < nblk, n_k = off[k+1] - off[k];
+ * rectangular when the sizes differ.  One pass, no n x n intermediate: an output element combines the at most 16 elements
+ * M[idx[I][p], idx[J][q]] of column I = off[kl] + i and J = off[kr] + j of T with conj(wt[I][p]) wt[J][q].  Every element of out is written,
+ * one writer each; a block of size 0 is legal and writes nothing.  A malformed off (not monotone from 0 to n) fills out -- n_kl x n_kr as off
+ * states them, each held inside [0, n] -- with NaN; idx is clamped into [0, n).  Traffic model (elements per matrix): at most 16 n_kl n_kr
+ * read, n_kl n_kr written: 17 (n / nblk)^2, about n^2 per pair for two mirrors (59 MB per complex128 matrix at n = 1922).  No workspace.
+ * trx_sym_fold_pair_bd: the same for a 2x2-block-diagonal M given as its four diagonals bd [4][batch][N] (d11, d12, d21, d22; n = 2 N; the
+ * layout of one block of trx_redheffer_halfspace's bd): the dense out [batch,n_kl,n_kr], zeros included.  Serves Vf^-1 (pair k, k'), the blocks
+ * of Sin / Sout and of a homogeneous layer's S-matrix (pair k, k).  Traffic model: the 4 N diagonal entries read, n_kl n_kr written.
+ * N <= 16384.
+ * All six: stream-ordered, no host synchronisation, deterministic, no atomics; complex64 and complex128; n^2 < 2^31, batch <= 65535,
+ * 1 <= nblk <= 4, else TRX_ERR_ARG (also for kl or kr outside [0, nblk)); batch = 0 returns TRX_OK without touching any buffer.  Element
+ * alignment suffices for every buffer but ws. */
 size_t trx_sym_fold_ws_bytes(int dtype, int n, int batch);
 int trx_sym_fold(int dtype, const void* A, int n, int batch, const int* idx, const void* wt, const int* off, int nblk, void* blocks, double* resid,
                  void* ws, size_t ws_bytes, void* stream);
@@ -404,6 +418,10 @@ int trx_sym_fold_backward(int dtype, const void* gblocks, int n, int batch, cons
                           void* stream);
 int trx_sym_unfold_backward(int dtype, const void* gW, const void* glam, int n, int batch, const int* idx, const void* wt, const int* off, int nblk,
                             void* gWk, void* glamk, void* stream);
+int trx_sym_fold_pair(int dtype, const void* M, int n, int batch, const int* idx, const void* wt, const int* off, int nblk, int kl, int kr,
+                      void* out, void* stream);
+int trx_sym_fold_pair_bd(int dtype, const void* bd, int N, int batch, const int* idx, const void* wt, const int* off, int nblk, int kl, int kr,
+                         void* out, void* stream);
 
 /* ---- thickness sweeps that reuse a layer's modes (no reference counterpart; what modal solvers offer as a layer-thickness scan) ----------------
  * The modes W, kz, V of a layer do not depend on its thickness d, only the diagonal phase X = exp(i omega kz d) does.  With F = Vf^-1 V (the
@@ -459,7 +477,7 @@ int trx_thickness_columns(int dtype, const void* rhoL, const void* rhoR, const v
  * 3 QR off-window update; 4 QR window chase; 5 Hessenberg gemv; 6 Hessenberg reflector column; 7 LU panel; 8 - 15 see trx_prof_tag_name;
  * 16 trx_sym_fold (both passes); 17 trx_sym_unfold (zero fill and scatter); 18 trx_thickness_prepare (whole call); 19 - 21 the stages of
  * trx_thickness_columns, one event pair per call each: 19 K assembly and its GEMMs, 20 LU of K and the column solve, 21 amplitudes and read-out;
- * 22 trx_sym_fold_backward; 23 trx_sym_unfold_backward. */
+ * 22 trx_sym_fold_backward; 23 trx_sym_unfold_backward; 24 trx_sym_fold_pair; 25 trx_sym_fold_pair_bd. */
 int trx_prof_enable(int on);
 int trx_prof_reset(void);
 int trx_prof_get(int tag, double* out);

@@ -94,7 +94,7 @@ class BatchedRCWA(FluxMixin, VolumeMixin):
     def __init__(self, freq, order, L, *, batch=None, dtype=torch.complex64, device=None, stable_eig_grad=True,
                  avoid_Pinv_instability=False, max_Pinv_instability=0.005, precision="high", engine=None,
                  keep_coupling=True, fold_layers=False, eig_route="auto", route_hint=None, fourier_rule="laurent", nv_sigma=NV_SIGMA_DEFAULT,
-                 symmetry=None, symmetry_tol=1e-6, symmetry_grad=False):
+                 symmetry=None, symmetry_tol=1e-6, symmetry_grad=False, symmetry_sector=False):
         check_fourier_rule(fourier_rule)
         # symmetry (extension): None | "x" | "y" | "xy" -- the caller states that every patterned layer is invariant under x -> -x (y -> -y) about
         # a plane and that kx0 = 0 (ky0 = 0) at every sweep point.  A = P Q of such a layer is then folded into 2 / 4 independent eigenproblems
@@ -113,6 +113,28 @@ class BatchedRCWA(FluxMixin, VolumeMixin):
         self.symmetry_grad = bool(symmetry_grad)
         if self.symmetry_grad and symmetry is None:
             raise ValueError('symmetry_grad=True needs symmetry="x" | "y" | "xy"')
+        # symmetry_sector=True (opt-in; needs symmetry=): the caller states that the WHOLE stack shares the mirrors.  The global S-matrix is then
+        # block diagonal in the mirror basis, and solve_S_parameters solves -- eigenproblem, layer S-matrices, star products -- only the sectors
+        # the requested columns touch (one of about n / 4 for an x- or y-polarised (0, 0) order under "xy").  A patterned layer keeps the folded
+        # P_k, Q_k of every block (include/trx.h: trx_sym_fold_pair) instead of P, Q, A and its modes; there is no global S-matrix, so
+        # everything that reads one is refused.  symmetry_residual is None for such layers: the grid check with
+        # symmetry_tol is the guard.  False: today's paths, untouched.
+        self.symmetry_sector = bool(symmetry_sector)
+        if self.symmetry_sector:
+            if symmetry is None:
+                raise ValueError('symmetry_sector=True needs symmetry="x" | "y" | "xy"')
+            if keep_coupling:
+                raise ValueError("symmetry_sector=True needs keep_coupling=False: the coupling matrices of a stack live in the original basis, "
+                                 "and a sector solve keeps none (the drop-in class rcwa always keeps them)")
+            if avoid_Pinv_instability is True:
+                raise ValueError("symmetry_sector=True is not available with avoid_Pinv_instability=True (a sector takes V = Q W Kz^-1 only)")
+            if self.symmetry_grad:
+                raise ValueError("symmetry_sector=True is not available on a differentiable stack (symmetry_grad=True): the adjoint of the "
+                                 "sector cascade is not implemented")
+        self._sector_centres = None      # (cx, nx, cy, ny) of the first patterned layer: the one plan of the whole stack
+        self._sector_layers = []         # per layer: dict(P=[P_k], Q=[Q_k]) of a patterned layer, None for a homogeneous one
+        self._sector_layer_S = {}        # (layer, block) -> [S11, S21] of the sector
+        self._sector_S = {}              # block -> the sector of the whole stack's S-matrix, [S11, S21, S12, S22]
         # fourier_rule="li" needs the rectangular order box on a rectangular lattice (ValueError otherwise, see the order / lattice below).
         # fourier_rule="li": Li's inverse rule for the x / y components of D in every patterned layer (Ex, Ey convolution matrices,
         # include/trx.h trx_convmat_li); Ez / Hz keep Laurent's matrices (E^-1 in P, trx_hmodes, eps_conv).  "laurent": the reference's rule.
@@ -239,9 +261,11 @@ class BatchedRCWA(FluxMixin, VolumeMixin):
     # ---- a2 / a3 -----------------------------------------------------------------------------------------
     def add_input_layer(self, eps=1., mu=1.):                                           # rcwa.py:95-107
         self.eps_in, self.mu_in, self.has_in = self._bvec(eps), self._bvec(mu), True
+        self._sector_S = {}
 
     def add_output_layer(self, eps=1., mu=1.):                                          # rcwa.py:109-121
         self.eps_out, self.mu_out, self.has_out = self._bvec(eps), self._bvec(mu), True
+        self._sector_S = {}
 
     def set_incident_angle(self, inc_ang, azi_ang, angle_layer="input"):                # rcwa.py:123-144
         self.inc_ang, self.azi_ang = self._bvec(inc_ang), self._bvec(azi_ang)
@@ -253,6 +277,7 @@ class BatchedRCWA(FluxMixin, VolumeMixin):
             warnings.warn("Invalid angle layer. Set as input layer.", UserWarning)
             self.angle_layer = "input"
         self._kvectors()
+        self._sector_S, self._sector_layer_S = {}, {}
         if self.symmetry is not None:
             # the mirror x -> -x maps kx0 + m Gx onto -(kx0 + m Gx) only for kx0 = 0 (ky0 is free: an angle sweep in the yz plane qualifies)
             bad = torch.stack([(k != 0).any() for k, nm in ((self.kx0_norm, "x"), (self.ky0_norm, "y")) if nm in self.symmetry]).cpu().tolist()
@@ -302,6 +327,8 @@ class BatchedRCWA(FluxMixin, VolumeMixin):
         plain layer, and solve_S_parameters returns [B, T, len(orders)] (one GEMM and one LU per thickness, include/trx.h:
         trx_thickness_prepare / trx_thickness_columns).  At most one swept layer; needs keep_coupling=False and a non-differentiable stack."""
         eng, N, B, cdt = self.engine, self.order_N, self.B, self._cdtype
+        if self.symmetry_sector:
+            return self._add_layer_sector(thickness, eps, mu, normal_field, swept)
         if swept:
             if self._swept is not None:
                 raise ValueError(f"add_layer(swept=True): layer {self._swept['index']} is already swept; one swept layer per solver "
@@ -471,7 +498,8 @@ class BatchedRCWA(FluxMixin, VolumeMixin):
                 return self._nv_tensor_torch(g, nn)
             return eng.convmat_nv(g, self.order[0], self.order[1], cdt, sigma=self.nv_sigma, hx=hx, hy=hy, nn=nn)
 
-        lean = (not diff) and (not self.keep_coupling) and mu_h and (not eps_h) and (not self.avoid_Pinv_instability)
+        lean = ((not diff) and (not self.keep_coupling) and mu_h and (not eps_h) and (not self.avoid_Pinv_instability)
+                and not self.symmetry_sector)                               # a sector layer folds the finished P, Q
         E, Einv, eps_s = conv(eps, eps_h)
         if lean:
             M, Minv, mu_s = None, None, self._bvec(mu)
@@ -782,6 +810,13 @@ class BatchedRCWA(FluxMixin, VolumeMixin):
         """The folding plan of a patterned layer: the centre c of every claimed mirror is detected from the layer's grids (ValueError if a grid
         does not have the mirror), and the plan of (c, grid size) is built once per solver."""
         key = _sym.grid_centres(grids, self.symmetry, self.symmetry_tol)
+        if self.symmetry_sector:
+            if self._sector_centres is None:
+                self._sector_centres = key
+            elif key != self._sector_centres:
+                raise ValueError(f'symmetry_sector=True: the mirror planes of this layer, (cx, nx, cy, ny) = {key}, differ from those of the first '
+                                 f"patterned layer, {self._sector_centres}: the sector cascade needs one symmetry basis for the whole stack "
+                                 "(sample every grid about the same centre)")
         if key not in self._sym_plans:
             self._sym_plans[key] = _sym.build_plan(self._mn, self.symmetry, *key)
         return self._sym_plans[key]
@@ -807,6 +842,126 @@ class BatchedRCWA(FluxMixin, VolumeMixin):
         pairs = [eig(Bk) if Bk.shape[-1] > 0 else (Bk.new_empty(Bk.shape[:2]), Bk) for Bk in blocks]
         lam, W = ag.SymUnfoldFn.apply(plan, eng, *[p[1] for p in pairs], *[p[0] for p in pairs])
         return lam, W, resid
+
+    # ---- sector solves (symmetry_sector=True) ------------------------------------------------------------
+    def _refuse_sector(self, what):
+        if self.symmetry_sector:
+            raise ValueError(f"{what} is not available with symmetry_sector=True: only the mirror sectors a source excites are solved, so there is "
+                             "no global S-matrix and there are no coupling matrices; solve_S_parameters(...) is the read-out of a sector solve")
+
+    def _add_layer_sector(self, thickness, eps, mu, normal_field, swept):
+        """add_layer of a sector solver: a patterned layer is factorised and its P, Q are built as always (any fourier_rule, a patterned mu),
+        then every block keeps P_k = T_k^H P T_k', Q_k = T_k'^H Q T_k and the full-size P, Q are dropped: no A, no eigen call here.  A
+        homogeneous layer keeps its block-diagonal S-matrix."""
+        eng = self.engine
+        if swept:
+            raise ValueError("add_layer(swept=True) is not available with symmetry_sector=True: the thickness sweep works on the modes of the "
+                             "original basis")
+        if normal_field is not None:
+            raise ValueError("symmetry= cannot be combined with add_layer(normal_field=...): a caller-supplied field is not checked for the mirror; "
+                             "let the field be derived from the grid")
+        if torch.is_grad_enabled() and any(torch.is_tensor(v) and v.requires_grad for v in
+                                           (thickness, eps, mu, self.freq, self.Kx_norm_dn, self.Ky_norm_dn)):
+            raise ValueError("symmetry_sector=True is not available on a differentiable stack (a tensor of this layer requires grad): the "
+                             "adjoint of the sector cascade is not implemented")
+        eps_h, mu_h = self._is_homogeneous(eps), self._is_homogeneous(mu)
+        self._sector_S = {}
+        self.symmetry_residual.append(None)
+        if eps_h and mu_h:
+            self._add_homogeneous_layer_bd(thickness, self._bvec(eps), self._bvec(mu))
+            self._sector_layers.append(None)
+            return
+        eye = torch.eye(self.order_N, dtype=self._cdtype, device=self._device)
+        fac, plan = self._factorise(eps, mu, eps_h, mu_h, None, False, eye)
+        if fac.Einv is None:
+            fac = fac._replace(Einv=eng.inverse(fac.E))
+        if fac.Minv is None:
+            fac = fac._replace(Minv=eng.inverse(fac.M))
+        P, Q = self._pq(fac, False)
+        del fac
+        opp = [_sym.opposite_block(plan.nblk, k) for k in range(plan.nblk)]
+        self._sector_layers.append(dict(P=[eng.sym_fold_pair(P, plan, k, opp[k]) for k in range(plan.nblk)],
+                                        Q=[eng.sym_fold_pair(Q, plan, opp[k], k) for k in range(plan.nblk)]))
+        del P, Q
+        self.layer_N += 1
+        self.thickness.append(self._bvec(thickness, self._rdtype))
+        self._append_none(self.eps_conv, self.mu_conv, self.eps_grid, self.mu_grid, self.eps_conv_x, self.eps_conv_y, self.eps_conv_xx, self.eps_conv_xy,
+                          self.eps_conv_yy, self.P, self.Q, self.kz_norm, self.E_eigvec, self.H_eigvec, self.Cplus, self.Cminus, self.layer_S11,
+                          self.layer_S21)
+
+    def _sector_plan(self):
+        """The one plan of the stack: that of the first patterned layer's centres; centres 0 when no layer is patterned."""
+        key = self._sector_centres if self._sector_centres is not None else (0, 1, 0, 1)
+        if key not in self._sym_plans:
+            self._sym_plans[key] = _sym.build_plan(self._mn, self.symmetry, *key)
+        return self._sym_plans[key]
+
+    def _sector_bd(self, blk, kl, kr):
+        """Dense sector block T_kl^H M T_kr of a BlockDiag2 M."""
+        return self.engine.sym_fold_pair_bd(torch.stack(blk.d, dim=0).to(self._cdtype).contiguous(), self._sector_plan(), kl, kr)
+
+    def _sector_layer(self, i, k):
+        """[S11, S21] of layer i in sector k (cached): the lean formulation of SURVEY.md section 7.2 on the folded operators, with
+        V_k = Q_k W_k Kz^-1 and the dense Vf^-1 block (k, k')."""
+        if (i, k) in self._sector_layer_S:
+            return self._sector_layer_S[(i, k)]
+        eng, rec = self.engine, self._sector_layers[i]
+        if rec is None:
+            S = [self._sector_bd(self.layer_S11[i], k, k), self._sector_bd(self.layer_S21[i], k, k)]
+        else:
+            plan = self._sector_plan()
+            A = eng.gemm(rec["P"][k], rec["Q"][k])
+            lam, W = self._eig_call(A, refine_steps=3 if self._dtype == torch.complex128 else 2)
+            del A
+            kz = torch.sqrt(lam)
+            kz = torch.where(torch.imag(kz) < 0, -kz, kz)                               # rcwa.py:1241
+            X = torch.exp(1j * (self.omega * self.thickness[i])[:, None] * kz)          # rcwa.py:1246
+            V = eng.gemm(rec["Q"][k], (W / kz[:, None, :]).contiguous())                # Q W Kz^-1, in the coordinates of block k'
+            F = eng.gemm(self._sector_bd(self._Vfinv, k, _sym.opposite_block(plan.nblk, k)), V)
+            A_, B_ = W + F, (W - F) * X[:, None, :]
+            I = torch.eye(W.shape[-1], dtype=self._cdtype, device=self._device).expand(self.B, -1, -1).contiguous()
+            Tip, Tim = eng.solve(A_ + B_, I), eng.solve(A_ - B_, I)
+            cp, cm = Tip + Tim, Tip - Tim
+            S = [eng.gemm(W, X[:, :, None] * cp + cm), eng.gemm(W, cp + X[:, :, None] * cm) - I]
+        self._sector_layer_S[(i, k)] = S
+        return S
+
+    def _sector_global(self, k):
+        """Sector k of the whole stack's S-matrix (cached): the Redheffer products of the layers' sectors and the folded half-spaces."""
+        if k in self._sector_S:
+            return self._sector_S[k]
+        eng = self.engine
+        S = None
+        for i in range(self.layer_N):
+            S11, S21 = self._sector_layer(i, k)
+            Si = [S11, S21, S21, S11]
+            S = Si if S is None else eng.redheffer(S, Si)[0]
+        if S is None:
+            nk = self._sector_plan().sizes[k]
+            I = torch.eye(nk, dtype=self._cdtype, device=self._device).expand(self.B, -1, -1).contiguous()
+            Z = torch.zeros_like(I)
+            S = [I, Z, Z.clone(), I.clone()]
+        if self.has_in:
+            S = eng.redheffer([self._sector_bd(blk, k, k) for blk in self._Sin], S)[0]
+        if self.has_out:
+            S = eng.redheffer(S, [self._sector_bd(blk, k, k) for blk in self._Sout])[0]
+        self._sector_S[k] = S
+        return S
+
+    def _solve_sector(self, orders, direction, port, polarization, ref_order, power_norm, evanscent):
+        """solve_S_parameters of a sector solver: column c of block kb of the global S-matrix is sum_k T_k S^(k)_kb T_k^H e_c over the sectors
+        that c touches; the expansion is plain indexing, O(n) per column, and a row no sector reaches is exactly 0."""
+        orders, polarization, oi, ri, kb = self._sparam_args(orders, direction, port, polarization, ref_order)
+        plan = self._sector_plan()
+        full = {}
+        for c in self._sparam_columns(ri, polarization):
+            col = torch.zeros((self.B, self.n), dtype=self._cdtype, device=self._device)
+            for k, j, w in _sym.sector_coordinates(plan, c):
+                rows, src, wts = plan.expansion(k, self._device, self._cdtype)
+                y = w * self._sector_global(k)[kb][:, :, j]
+                col[:, rows] += wts[None, :] * y[:, src]
+            full[c] = col
+        return self._sparam_values(lambda c: full[c], kb, oi, ri, polarization, power_norm, evanscent)
 
     def _is_homogeneous(self, v):
         if isinstance(v, (float, complex)):
@@ -952,6 +1107,7 @@ class BatchedRCWA(FluxMixin, VolumeMixin):
 
     def solve_global_smatrix(self):                                                     # rcwa.py:173-211
         self._refuse_swept("solve_global_smatrix")
+        self._refuse_sector("solve_global_smatrix")
         S, C, _ = self._cascade()
         if self._is_bd(S):                                                              # only homogeneous media: densify for the read-out
             S = [blk.dense().to(self._cdtype) for blk in S]
@@ -966,7 +1122,11 @@ class BatchedRCWA(FluxMixin, VolumeMixin):
         read-out takes are computed (Engine.redheffer_halfspace_columns: one LU instead of the 4.33 n^3 product), and `self.S` / `self.C` are
         NOT set (they keep whatever an earlier solve_global_smatrix left).  Every other case -- keep_coupling, a differentiable stack, no
         half-space, only homogeneous layers -- runs solve_global_smatrix() and reads out of self.S as S_parameters does.
-        On a solver with a swept layer (add_layer(..., swept=True)) the result is [B, T, len(orders)], one row per thickness."""
+        On a solver with a swept layer (add_layer(..., swept=True)) the result is [B, T, len(orders)], one row per thickness.
+        With symmetry_sector=True only the mirror sectors that the requested columns touch are solved, cached per (layer, sector), and
+        `self.S` / `self.C` are not set."""
+        if self.symmetry_sector:
+            return self._solve_sector(orders, direction, port, polarization, ref_order, power_norm, evanscent)
         if self._swept is not None:
             return self._solve_swept(orders, direction, port, polarization, ref_order, power_norm, evanscent)
         orders, polarization, oi, ri, k = self._sparam_args(orders, direction, port, polarization, ref_order)
@@ -1039,6 +1199,7 @@ class BatchedRCWA(FluxMixin, VolumeMixin):
 
     def S_parameters(self, orders, *, direction="forward", port="transmission", polarization="xx", ref_order=[0, 0],
                      power_norm=True, evanscent=1e-3):                                  # rcwa.py:300-524
+        self._refuse_sector("S_parameters")
         orders, polarization, oi, ri, k = self._sparam_args(orders, direction, port, polarization, ref_order)
         Sk = self.S[k]
         return self._sparam_values(lambda c: Sk[:, :, c], k, oi, ri, polarization, power_norm, evanscent)
@@ -1140,9 +1301,10 @@ class BatchedRCWA(FluxMixin, VolumeMixin):
 
 
 def _refusing_swept(name):
-    """The mixin method `name`, refused on a solver with a swept layer."""
+    """The mixin method `name`, refused on a solver with a swept layer or in sector mode."""
     def method(self, *a, **kw):
         self._refuse_swept(name)
+        self._refuse_sector(name)
         return getattr(super(BatchedRCWA, self), name)(*a, **kw)
     method.__name__ = name
     return method
@@ -1150,3 +1312,16 @@ def _refusing_swept(name):
 
 for _name in ("power_flux", "incident_flux", "absorption", "volume_integral", "absorption_by_region"):
     setattr(BatchedRCWA, _name, _refusing_swept(_name))
+
+
+def _refusing_sector(name):
+    """The mixin method `name`, refused in sector mode."""
+    def method(self, *a, **kw):
+        self._refuse_sector(name)
+        return getattr(super(BatchedRCWA, self), name)(*a, **kw)
+    method.__name__ = name
+    return method
+
+
+for _name in ("source_planewave", "source_fourier"):
+    setattr(BatchedRCWA, _name, _refusing_sector(_name))

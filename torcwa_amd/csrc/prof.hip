@@ -116,6 +116,7 @@ extern "C" const char* trx_prof_tag_name(int tag) {
                                             "phase:balance", "phase:hessenberg", "phase:qr", "phase:schur_vectors", "phase:refinement",
                                             "sym_fold", "sym_unfold",
                                             "thickness_prepare", "thickness_columns:K_gemm", "thickness_columns:lu_solve", "thickness_columns:readout",
-                                            "sym_fold_backward", "sym_unfold_backward"};
+                                            "sym_fold_backward", "sym_unfold_backward",
+                                            "sym_fold_pair", "sym_fold_pair_bd"};
     return (tag >= 0 && tag < PROF_NTAGS) ? names[tag] : "?";
 }

@@ -15,7 +15,9 @@ enum ProfTag { PROF_GEMM_NN = 0, PROF_GEMM_OTHER = 1, PROF_QR_PREPARE = 2, PROF_
                // trx_thickness_columns (K assembly and its GEMMs; LU of K and the solve; amplitudes and read-out)
                PROF_THICK_PREPARE = 18, PROF_THICK_KGEMM = 19, PROF_THICK_LU = 20, PROF_THICK_READOUT = 21,
                // adjoints of the folding (symfold.hip): trx_sym_fold_backward, trx_sym_unfold_backward
-               PROF_SYM_FOLD_BWD = 22, PROF_SYM_UNFOLD_BWD = 23, PROF_NTAGS = 24 };
+               PROF_SYM_FOLD_BWD = 22, PROF_SYM_UNFOLD_BWD = 23,
+               // sector folds (symfold.hip): trx_sym_fold_pair, trx_sym_fold_pair_bd
+               PROF_SYM_FOLD_PAIR = 24, PROF_SYM_FOLD_PAIR_BD = 25, PROF_NTAGS = 26 };
 // (PROF_GEMM_*_F32: the fp32 GEMMs -- first stage of the mixed-precision eigensolver, precision="native" -- are counted apart from the fp64 ones:
 // other peak, other roofline)
 

@@ -27,6 +27,16 @@
 // distinct elements are sum_k n_k^2 ~ n^2 / nblk and the re-reads of an orbit fall in the same rows) and 2 n plan rows per SF_ROWS rows:
 // counted as (1 + nblk) n^2.  unfold backward reads every element of gW once (n^2: the supports of the columns of one block are disjoint) and
 // writes sum_k n_k^2 ~ n^2 / nblk: (1 + 1 / nblk) n^2.
+//
+// Sector folds (trx_sym_fold_pair, trx_sym_fold_pair_bd): out = T_kl^H M T_kr for ONE pair of blocks, rectangular when their sizes differ.
+//   One pass, no n x n intermediate: out[i, j] = sum_p sum_q conj(wt[I][p]) M[idx[I][p], idx[J][q]] wt[J][q], I = off[kl] + i, J = off[kr] + j:
+//   at most 16 elements of M per output element.  A workgroup owns SF_ROWS output rows and stages their plan entries in LDS once; the lanes of a
+//   wave walk j, so the gathers of one output row stay inside the at most four rows idx[I][p] of M and the writes are coalesced.  _bd: M is
+//   2x2-block-diagonal and given as its four diagonals [4][batch][N]; element (r, c) is d[2 (r >= N) + (c >= N)][r mod N] where r = c mod N,
+//   0 elsewhere; the dense n_kl x n_kr result is written, zeros included.  The block sizes live in device memory (off), so the grid covers
+//   ceil(n / SF_ROWS) row groups and the groups beyond n_kl leave at once.  No workspace, no atomics: every element has one writer.
+// Traffic model per matrix: at most 16 n_kl n_kr elements read and n_kl n_kr written, 17 (n / nblk)^2: about n^2 per pair for two mirrors.  _bd
+//   reads the 4 N diagonal entries (the 16 candidates of an element are index tests, not loads) and writes n_kl n_kr.
 #include "common.hpp"
 #include "prof.hpp"
 
@@ -312,6 +322,88 @@ __global__ __launch_bounds__(SF_THREADS) void sym_unfold_bwd_kernel(const cx<T>*
     }
 }
 
+// The extent of blocks kl (rows) and kr (columns) of a sector fold, from off as given: n_k = off[k+1] - off[k], held inside [0, n] so that a
+// malformed off (ok = 0) still names the out array the caller sized from the same numbers.
+struct PairExtent {
+    int ok, ol, nl, oc, nr;
+};
+
+__device__ __forceinline__ PairExtent pair_extent(const int* __restrict__ off, int nblk, int n, int kl, int kr) {
+    PairExtent E;
+    E.ok = off[0] == 0 && off[nblk] == n;
+    for (int k = 0; k < nblk; ++k) E.ok = E.ok && off[k + 1] >= off[k];
+    E.ol = off[kl];
+    E.oc = off[kr];
+    const long dl = (long)off[kl + 1] - E.ol, dr = (long)off[kr + 1] - E.oc;
+    E.nl = dl < 0 ? 0 : (dl > n ? n : (int)dl);
+    E.nr = dr < 0 ? 0 : (dr > n ? n : (int)dr);
+    return E;
+}
+
+// out[b] = T_kl^H M[b] T_kr.  grid (ceil(n / SF_ROWS), batch).  BD: src = the four diagonals [4][batch][N] of a 2x2-block-diagonal M, n = 2 N.
+template <class T, bool BD>
+__global__ __launch_bounds__(SF_THREADS) void sym_fold_pair_kernel(const cx<T>* __restrict__ src, const int* __restrict__ idx,
+                                                                   const cx<T>* __restrict__ wt, const int* __restrict__ off, int nblk, int n,
+                                                                   int batch, int kl, int kr, cx<T>* __restrict__ out) {
+    __shared__ int srow[SF_ROWS * 4];
+    __shared__ T swx[SF_ROWS * 4], swy[SF_ROWS * 4];
+    const int tid = threadIdx.x, b = blockIdx.y, i0 = blockIdx.x * SF_ROWS;
+    const PairExtent E = pair_extent(off, nblk, n, kl, kr);
+    if (i0 >= E.nl || E.nr == 0) return;                                                // the whole workgroup: before any barrier
+    const int rows = E.nl - i0 < SF_ROWS ? E.nl - i0 : SF_ROWS;
+    cx<T>* ob = out + ((long)b * E.nl + i0) * E.nr;
+    if (!E.ok) {
+        const T bad = (T)__builtin_nan("");
+        for (long e = tid; e < (long)rows * E.nr; e += SF_THREADS) ob[e] = cx<T>(bad, bad);
+        return;
+    }
+    if (tid < rows * 4) {                                                               // the plan entries of this group's rows, once
+        const int I = E.ol + i0 + (tid >> 2);
+        const cx<T> w = conj(wt[I * 4 + (tid & 3)]);
+        srow[tid] = clamp_row(idx[I * 4 + (tid & 3)], n);
+        swx[tid] = w.x;
+        swy[tid] = w.y;
+    }
+    __syncthreads();
+    const int N = n >> 1;
+    const cx<T>* Mb = BD ? src + (long)b * N : src + (long)b * n * n;
+    for (int j = tid; j < E.nr; j += SF_THREADS) {
+        const int J = E.oc + j;
+        int c[4];
+        cx<T> w[4];
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            c[q] = clamp_row(idx[J * 4 + q], n);
+            w[q] = wt[J * 4 + q];
+        }
+        for (int rr = 0; rr < rows; ++rr) {
+            cx<T> acc(T(0), T(0));
+#pragma unroll
+            for (int p = 0; p < 4; ++p) {
+                const cx<T> wl(swx[rr * 4 + p], swy[rr * 4 + p]);
+                if (!nonzero(wl)) continue;                                             // wave-uniform
+                const int r = srow[rr * 4 + p];
+                cx<T> s(T(0), T(0));
+                if (BD) {
+                    const int rm = r >= N ? r - N : r;
+#pragma unroll
+                    for (int q = 0; q < 4; ++q) {
+                        const int cm = c[q] >= N ? c[q] - N : c[q];
+                        if (nonzero(w[q]) && cm == rm) cfma(s, Mb[(long)(2 * (r >= N) + (c[q] >= N)) * batch * N + rm], w[q]);
+                    }
+                } else {
+                    const cx<T>* Mrow = Mb + (long)r * n;
+#pragma unroll
+                    for (int q = 0; q < 4; ++q)
+                        if (nonzero(w[q])) cfma(s, Mrow[c[q]], w[q]);
+                }
+                cfma(acc, wl, s);
+            }
+            ob[(long)rr * E.nr + j] = acc;
+        }
+    }
+}
+
 size_t part_bytes(int n, int batch) { return sizeof(double) * 2 * (size_t)cdiv_i(n, SF_ROWS) * (size_t)batch; }
 
 template <class T>
@@ -360,6 +452,18 @@ int sym_unfold_bwd_t(hipStream_t st, const cx<T>* gW, const cx<T>* glam, int n, 
     ProfScope prof(PROF_SYM_UNFOLD_BWD, st, 8.0 * nn, sizeof(cx<T>) * (1.0 + 1.0 / nblk) * nn);
     TRX_LAUNCH((sym_unfold_bwd_kernel<T>), dim3(cdiv_i(n, SF_ROWS), batch), dim3(SF_THREADS), 0, st, gW, glam, idx, wt, off, nblk, n, batch, gWk,
                glamk);
+    TRX_CHECK_LAUNCH();
+    return TRX_OK;
+}
+
+template <class T, bool BD>
+int sym_fold_pair_t(hipStream_t st, const cx<T>* src, int n, int batch, const int* idx, const cx<T>* wt, const int* off, int nblk, int kl, int kr,
+                    cx<T>* out) {
+    const double blk = ((double)n / nblk) * ((double)n / nblk) * batch;                 // n_kl n_kr of the model: the sizes stay on the device
+    ProfScope prof(BD ? PROF_SYM_FOLD_PAIR_BD : PROF_SYM_FOLD_PAIR, st, 8.0 * 20.0 * blk,
+                   sizeof(cx<T>) * (BD ? 2.0 * n * batch + blk : 17.0 * blk));
+    TRX_LAUNCH((sym_fold_pair_kernel<T, BD>), dim3(cdiv_i(n, SF_ROWS), batch), dim3(SF_THREADS), 0, st, src, idx, wt, off, nblk, n, batch, kl, kr,
+               out);
     TRX_CHECK_LAUNCH();
     return TRX_OK;
 }
@@ -431,4 +535,33 @@ extern "C" int trx_sym_unfold_backward(int dtype, const void* gW, const void* gl
                                        (cx<float>*)gWk, (cx<float>*)glamk);
     return sym_unfold_bwd_t<double>(st, (const cx<double>*)gW, (const cx<double>*)glam, n, batch, idx, (const cx<double>*)wt, off, nblk,
                                     (cx<double>*)gWk, (cx<double>*)glamk);
+}
+
+extern "C" int trx_sym_fold_pair(int dtype, const void* M, int n, int batch, const int* idx, const void* wt, const int* off, int nblk, int kl, int kr,
+                                 void* out, void* stream) {
+    const int rc = check_common(dtype, n, batch, nblk);
+    if (rc != TRX_OK) return rc;
+    if (kl < 0 || kl >= nblk || kr < 0 || kr >= nblk) return TRX_ERR_ARG;
+    if (batch == 0) return TRX_OK;
+    if (!M || !idx || !wt || !off || !out) return TRX_ERR_ARG;
+    hipStream_t st = trx::api_stream(stream);
+    if (dtype == TRX_C64)
+        return sym_fold_pair_t<float, false>(st, (const cx<float>*)M, n, batch, idx, (const cx<float>*)wt, off, nblk, kl, kr, (cx<float>*)out);
+    return sym_fold_pair_t<double, false>(st, (const cx<double>*)M, n, batch, idx, (const cx<double>*)wt, off, nblk, kl, kr, (cx<double>*)out);
+}
+
+extern "C" int trx_sym_fold_pair_bd(int dtype, const void* bd, int N, int batch, const int* idx, const void* wt, const int* off, int nblk, int kl,
+                                    int kr, void* out, void* stream) {
+    if (dtype != TRX_C64 && dtype != TRX_C128) return TRX_ERR_DTYPE;
+    if (N < 1 || N > (1 << 14)) return TRX_ERR_ARG;
+    const int n = 2 * N;
+    const int rc = check_common(dtype, n, batch, nblk);
+    if (rc != TRX_OK) return rc;
+    if (kl < 0 || kl >= nblk || kr < 0 || kr >= nblk) return TRX_ERR_ARG;
+    if (batch == 0) return TRX_OK;
+    if (!bd || !idx || !wt || !off || !out) return TRX_ERR_ARG;
+    hipStream_t st = trx::api_stream(stream);
+    if (dtype == TRX_C64)
+        return sym_fold_pair_t<float, true>(st, (const cx<float>*)bd, n, batch, idx, (const cx<float>*)wt, off, nblk, kl, kr, (cx<float>*)out);
+    return sym_fold_pair_t<double, true>(st, (const cx<double>*)bd, n, batch, idx, (const cx<double>*)wt, off, nblk, kl, kr, (cx<double>*)out);
 }

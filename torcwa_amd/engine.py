@@ -796,6 +796,48 @@ class Engine:
                                                     plan.nblk, Wp.data_ptr(), lp.data_ptr(), self.stream))
         return Wk, lamk
 
+    # -- sector folds ------------------------------------------------------------------------------------
+    @_phase("symmetry sector fold (trx_sym_fold_pair)")
+    def sym_fold_pair(self, M, plan, kl, kr):
+        """[B, n_kl, n_kr] = T_kl^H M T_kr for M [B,n,n] and one pair of blocks of a SymPlan (include/trx.h: trx_sym_fold_pair).  M is not
+        modified and need not commute with the mirrors."""
+        M = self._c(M)
+        self._check(M)
+        B, n, _ = M.shape
+        if n != plan.n or M.shape[2] != n:
+            raise ValueError(f"sym_fold_pair: M is {list(M.shape[1:])}, the plan is for n = {plan.n}")
+        kl, kr = self._pair(plan, kl, kr)
+        dt = M.dtype
+        idx, wt, off = plan.device(self.device, dt)
+        out = torch.empty((B, plan.sizes[kl], plan.sizes[kr]), dtype=dt, device=self.device)
+        self.lib.check(self.lib.sym_fold_pair(_CODE[dt], M.data_ptr(), n, B, idx.data_ptr(), wt.data_ptr(), off.data_ptr(), plan.nblk, kl, kr,
+                                              out.data_ptr(), self.stream))
+        return out
+
+    @_phase("symmetry sector fold (trx_sym_fold_pair)")
+    def sym_fold_pair_bd(self, bd, plan, kl, kr):
+        """sym_fold_pair of a 2x2-block-diagonal operator given as its four diagonals bd [4,B,N] (BlockDiag2.d stacked): the dense
+        [B, n_kl, n_kr] block (include/trx.h: trx_sym_fold_pair_bd)."""
+        bd = self._c(bd)
+        self._check(bd)
+        if bd.dim() != 3 or bd.shape[0] != 4 or 2 * bd.shape[2] != plan.n:
+            raise ValueError(f"sym_fold_pair_bd: bd must be [4, B, {plan.n // 2}], got {list(bd.shape)}")
+        _, B, N = bd.shape
+        kl, kr = self._pair(plan, kl, kr)
+        dt = bd.dtype
+        idx, wt, off = plan.device(self.device, dt)
+        out = torch.empty((B, plan.sizes[kl], plan.sizes[kr]), dtype=dt, device=self.device)
+        self.lib.check(self.lib.sym_fold_pair_bd(_CODE[dt], bd.data_ptr(), N, B, idx.data_ptr(), wt.data_ptr(), off.data_ptr(), plan.nblk, kl, kr,
+                                                 out.data_ptr(), self.stream))
+        return out
+
+    @staticmethod
+    def _pair(plan, kl, kr):
+        kl, kr = int(kl), int(kr)
+        if not (0 <= kl < plan.nblk and 0 <= kr < plan.nblk):
+            raise ValueError(f"blocks ({kl}, {kr}) outside the plan's {plan.nblk}")
+        return kl, kr
+
 
 _default = None
 

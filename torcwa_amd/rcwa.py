@@ -15,7 +15,7 @@ pi = PI_REF
 class rcwa(FieldMixin):
     def __init__(self, freq, order, L, *, dtype=torch.complex64, device=None, stable_eig_grad=True,
                  avoid_Pinv_instability=False, max_Pinv_instability=0.005, precision="high", engine=None, fourier_rule="laurent",
-                 nv_sigma=NV_SIGMA_DEFAULT, symmetry=None, symmetry_tol=1e-6, symmetry_grad=False):
+                 nv_sigma=NV_SIGMA_DEFAULT, symmetry=None, symmetry_tol=1e-6, symmetry_grad=False, symmetry_sector=False):
         # fourier_rule (extension, keyword-only): "laurent" (the reference's factorisation) or "li" (Li's inverse rule for the in-plane
         # field components of every patterned layer; faster convergence in the order for high-contrast gratings) or "normal"
         # (the normal-vector method for curved / oblique boundaries; field smoothed over nv_sigma grid cells, or add_layer(normal_field=...))
@@ -23,6 +23,11 @@ class rcwa(FieldMixin):
         # 2 / 4 independent blocks (BatchedRCWA).  symmetry_residual: per layer the discarded part, or None.
         # symmetry_grad=True (opt-in) lets a differentiable stack use the fold: the eigen-part of the gradient is then the one of the
         # mirror-constrained problem.
+        # symmetry_sector: refused -- the drop-in keeps the coupling matrices (fields, flux), a sector solve has none (BatchedRCWA)
+        if symmetry_sector:
+            raise ValueError("symmetry_sector=True is not available on the drop-in class rcwa: it keeps the coupling matrices of the stack "
+                             "(keep_coupling=True) and a global S-matrix, a sector solve has neither; use BatchedRCWA(..., keep_coupling=False) "
+                             "or the sweep drivers")
         self._b = BatchedRCWA(freq, order, L, batch=1, dtype=dtype, device=device, stable_eig_grad=stable_eig_grad,
                               avoid_Pinv_instability=avoid_Pinv_instability, max_Pinv_instability=max_Pinv_instability,
                               precision=precision, engine=engine, fourier_rule=fourier_rule,

@@ -79,12 +79,12 @@ def rectangle_density(nx, ny, Lx, Ly, Wx, Wy, Cx, Cy, theta=0.0, edge_sharpness=
 
 def _solve_chunk(freq, layers, order, L, eps_in, eps_out, inc_ang, azi_ang, dtype, precision, engine, orders,
                  polarization, direction, port, check_info, eig_route="auto", route_hint=None, fourier_rule="laurent", nv_sigma=NV_SIGMA_DEFAULT,
-                 absorption=False, source=None, symmetry=None, symmetry_tol=1e-6):
+                 absorption=False, source=None, symmetry=None, symmetry_tol=1e-6, symmetry_sector=False):
     """layers: list of (thickness, eps[, mu]); thickness scalar or [b]; eps/mu scalar, [b] or [b,nx,ny].  absorption: the chunk keeps W, V and
     the coupling matrices (keep_coupling=True, no streaming cascade) and returns (S-parameters, BatchedRCWA.absorption())."""
     sim = BatchedRCWA(freq, order, L, dtype=dtype, precision=precision, engine=engine, keep_coupling=bool(absorption), fold_layers=not absorption,
                       eig_route=eig_route, route_hint=route_hint, fourier_rule=fourier_rule, nv_sigma=nv_sigma,
-                      symmetry=symmetry, symmetry_tol=symmetry_tol)
+                      symmetry=symmetry, symmetry_tol=symmetry_tol, **({"symmetry_sector": True} if symmetry_sector else {}))
     if eps_in is not None:
         sim.add_input_layer(eps=eps_in)
     if eps_out is not None:
@@ -203,7 +203,7 @@ def _source_amplitudes(source, B):
 def solve_stack_sweep(freq, layers, order, L, *, eps_in=None, eps_out=None, inc_ang=0.0, azi_ang=0.0, dtype=torch.complex64,
                       precision="high", engine=None, chunk=None, streams=1, orders=((0, 0),), polarization="xx",
                       direction="forward", port="transmission", check_info=True, eig_route="auto", fourier_rule="laurent",
-                      nv_sigma=NV_SIGMA_DEFAULT, absorption=False, source=None, symmetry=None, symmetry_tol=1e-6):
+                      nv_sigma=NV_SIGMA_DEFAULT, absorption=False, source=None, symmetry=None, symmetry_tol=1e-6, symmetry_sector=False):
     """B sweep points of a multi-layer stack (BASELINE.json configs 2-4): the reference's per-point Python loop
     (example/Example1-1.ipynb, Example3.ipynb) as chunks of a batched solve.  `layers` as in `_solve_chunk`, with
     per-point quantities carrying a leading dimension B = len(freq).  Returns the requested S-parameter [B, len(orders)].
@@ -218,6 +218,10 @@ def solve_stack_sweep(freq, layers, order, L, *, eps_in=None, eps_out=None, inc_
     folded into 2 / 4 independent blocks (BatchedRCWA, torcwa_amd/symmetry.py).  ValueError from the first chunk if a grid, the order set, the
     lattice or an angle does not have the mirror; symmetry_tol: the relative grid asymmetry that is accepted (and symmetrised away).
 
+    symmetry_sector=True (needs symmetry=, every patterned layer about the same mirror planes; not with absorption=True): only the mirror
+    sectors the requested columns excite are solved -- eigenproblem, layer S-matrices and star products of about n / 4 for an x- or
+    y-polarised (0, 0) order under "xy" (BatchedRCWA).
+
     absorption=True: every chunk is solved with keep_coupling=True and without the streaming cascade (more HBM per point: auto_chunk), the source
     is applied -- `source`: keywords of BatchedRCWA.source_planewave, or of source_fourier when it has "orders"; default a unit plane wave,
     amplitude [1, 0], notation "xy", in the call's `direction`; an amplitude with a leading B is cut into the chunks like every other per-point
@@ -226,6 +230,10 @@ def solve_stack_sweep(freq, layers, order, L, *, eps_in=None, eps_out=None, inc_
     default absorption=False the code path, the return value and the memory model are unchanged."""
     from .engine import default_engine
     check_fourier_rule(fourier_rule)
+    if symmetry_sector and absorption:
+        raise ValueError("symmetry_sector=True is not available with absorption=True: a sector solve keeps no coupling matrices")
+    if symmetry_sector and symmetry is None:
+        raise ValueError('symmetry_sector=True needs symmetry="x" | "y" | "xy"')
     B = freq.shape[0]
     eng = engine if engine is not None else default_engine()
     old_check, eng.check_info = eng.check_info, check_info         # restored below: the engine may be shared with other solvers
@@ -250,7 +258,7 @@ def solve_stack_sweep(freq, layers, order, L, *, eps_in=None, eps_out=None, inc_
                                _slice(azi_ang, lo, hi, B), dtype, precision, engine, orders, polarization, direction, port, check_info,
                                eig_route=eig_route, route_hint=route_hint, fourier_rule=fourier_rule, nv_sigma=nv_sigma,
                                **({"absorption": True, "source": src} if absorption else {}),
-                               symmetry=symmetry, symmetry_tol=symmetry_tol)
+                               symmetry=symmetry, symmetry_tol=symmetry_tol, **({"symmetry_sector": True} if symmetry_sector else {}))
 
     dev = freq.device
     try:

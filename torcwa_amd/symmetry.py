@@ -84,6 +84,17 @@ class SymPlan:
                                    torch.as_tensor(self._rows[1], device=device).to(dtype).contiguous())
         return self._rows_dev[key]
 
+    def expansion(self, k, device, dtype):
+        """(rows, src, w) of x = T_k y as plain indexing, x[rows] += w * y[src]: the non-zeros of block k's columns (rows int64 in [0, n), src
+        int64 local to the block, w in `dtype`).  The rows of one block are distinct (disjoint supports).  Tensors on `device`, cached."""
+        key = ("expand", k, str(device), dtype)
+        if key not in self._dev:
+            J, q = np.nonzero(self.wt[self.off[k]:self.off[k + 1]] != 0)
+            rows = self.idx[self.off[k] + J, q].astype(np.int64)
+            self._dev[key] = (torch.as_tensor(rows, device=device), torch.as_tensor(J.astype(np.int64), device=device),
+                              torch.as_tensor(self.wt[self.off[k] + J, q], device=device).to(dtype))
+        return self._dev[key]
+
     def dense(self, dtype=np.clongdouble):
         """T as a dense [n, n] numpy array (tests, diagnostics)."""
         T = np.zeros((self.n, self.n), dtype=dtype)
@@ -92,6 +103,23 @@ class SymPlan:
                 if self.wt[j, q] != 0:
                     T[self.idx[j, q], j] += self.wt[j, q]
         return T
+
+
+def opposite_block(nblk, k):
+    """The block k' that an E -> H or H -> E operator (Q, Vf; P, Vf^-1) connects block k with: H is a pseudovector, so its mirror eigenvalues are
+    minus those of E.  k' = 3 - k for two mirrors (_CLASS), 1 - k for one; block k' has the size of block k."""
+    if nblk not in (2, 4) or not (0 <= k < nblk):
+        raise ValueError(f"opposite_block: block {k} of {nblk}")
+    return nblk - 1 - k
+
+
+def sector_coordinates(plan, c):
+    """T^H e_c, the unit vector of row c of the original basis in the sectors: [(k, j, w)] with w = conj(T[c, off[k] + j]) for every block k that
+    has a column holding row c (at most one per block, SymPlan.rows).  The x / y component of order (0, 0) is one entry of weight 1."""
+    ridx, rwt = plan.rows()
+    if not (0 <= int(c) < plan.n):
+        raise ValueError(f"sector_coordinates: column {c} outside [0, {plan.n})")
+    return [(k, int(ridx[c, k] - plan.off[k]), complex(np.conj(rwt[c, k]))) for k in range(plan.nblk) if rwt[c, k] != 0]
 
 
 def build_plan(mn, symmetry, cx=0, nx=1, cy=0, ny=1):
