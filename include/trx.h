@@ -68,10 +68,12 @@ int trx_convmat_orders(int dtype, int grid_is_complex, const void* grid, int bat
  * where Toeplitz_x(f)[m,m'] = fhat[m-m'] of the 1-D DFT along x divided by nx ((2ox+1)^2), Toeplitz_y likewise ((2oy+1)^2).  Ex multiplies the
  * x component of E (inverse rule across the x discontinuities), Ey the y component.  Ex, Ey: [batch,N,N] outputs in `dtype`.
  * Ux [batch,nx,2oy+1,2oy+1], Uy [batch,ny,2ox+1,2ox+1]: optional complex128 outputs of the small inverses (NULL: not kept; the adjoint needs
- * them).  info[batch] (device): 0 ok, 1 a grid value is zero, 2 a Toeplitz block is singular.  All arithmetic is fp64 for both dtypes.
+ * them).  info[batch] (device): 0 ok, 1 a grid value is zero (it stays 1 although the block of that row then fails too), 2 a Toeplitz block
+ * is singular.  All arithmetic is fp64 for both dtypes and in the same order: a complex64 call returns the complex128 result, rounded once.
  * Requires nx > 2ox, ny > 2oy and max(nx, ny) <= 2048 (as trx_convmat); 2*max(ox,oy)+1 <= 99, i.e. max(ox,oy) <= 49 (one Toeplitz block of
  * (2o+1)^2 complex128 elements is held in the LDS of one CU, 160 KiB on gfx950), else TRX_ERR_UNSUPPORTED.  The workspace holds the pruned
- * DFTs of 1/grid, the per-direction transforms and, unless Ux / Uy are given, the inverses of a chunk of rows no larger than one output. */
+ * DFTs of 1/grid, the per-direction transforms and, unless Ux / Uy are given, the inverses of a chunk of rows no larger than one complex64 output
+ * (the same chunk for both dtypes). */
 size_t trx_convmat_li_ws_bytes(int dtype, int batch, int nx, int ny, int ox, int oy);
 int trx_convmat_li(int dtype, int grid_is_complex, const void* grid, int batch, int nx, int ny, int ox, int oy, void* Ex, void* Ey,
                    void* Ux, void* Uy, int* info, void* ws, size_t ws_bytes, void* stream);

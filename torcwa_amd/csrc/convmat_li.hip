@@ -155,8 +155,9 @@ __global__ __launch_bounds__(256) void toeplitz_inv_kernel(const zc* __restrict_
         }
         __syncthreads();
     }
-    if (singular) {
-        if (tid == 0) info[b] = 2;
+    if (singular) {                                // a zero grid value (info 1, set by recip_dft_y_kernel before) makes its row's block NaN,
+        if (tid == 0 && info[b] == 0) info[b] = 2; // which ends here too: the cause stays on record.  Benign race: the workgroups of
+                                                   // one b all store the same 2, and only over 0
         return;
     }
     for (int k = w - 1; k >= 0; --k) {             // A^-1 = (P A)^-1 P: the row interchanges become column interchanges
@@ -206,18 +207,18 @@ struct LiLayout {                    // workspace carving of trx_convmat_li (ele
     int rc_y, rc_x;                  // rows per chunk of the Toeplitz inverses when U is not an output
 };
 
-LiLayout li_layout(int dtype, int batch, int nx, int ny, int ox, int oy) {
+LiLayout li_layout(int batch, int nx, int ny, int ox, int oy) {
     LiLayout L;
     const long wx = 2 * ox + 1, wy = 2 * oy + 1, np = 4 * ox + 1, nq = 4 * oy + 1, N = wx * wy;
-    const long esz = dtype == TRX_C128 ? 16 : 8;
     L.ay = (long)batch * ny * np;
     L.ax = (long)batch * nx * nq;
     L.wy_tw = (long)ny * nq;
     L.wx_tw = (long)nx * np;
     L.F = (long)batch * wx * wx * nq;
     L.G = (long)batch * wy * wy * np;
-    // chunk of rows whose inverses are held at once: at most one output's size (B N^2 elements of the compute dtype), at least one row
-    const long cap = N * N * esz / 16;
+    // chunk of rows whose inverses are held at once: at most one complex64 output's size (B N^2 x 8 B), at least one row.  The same for
+    // both dtypes: the chunks fix the order of the fp64 accumulation, and a complex64 call must return the rounded complex128 result.
+    const long cap = N * N / 2;
     L.rc_y = (int)std::max(1L, std::min((long)ny, cap / (wx * wx)));
     L.rc_x = (int)std::max(1L, std::min((long)nx, cap / (wy * wy)));
     L.U = (long)batch * std::max((long)L.rc_y * wx * wx, (long)L.rc_x * wy * wy);
@@ -250,8 +251,8 @@ int li_direction(hipStream_t s, const zc* coef, int nrows, int w, const zc* Wtw,
 
 template <class T>
 int convmat_li_t(int cplx, const void* grid, int batch, int nx, int ny, int ox, int oy, void* Ex, void* Ey, void* Ux, void* Uy, int* info,
-                 void* ws, int dtype, hipStream_t s) {
-    const LiLayout L = li_layout(dtype, batch, nx, ny, ox, oy);
+                 void* ws, hipStream_t s) {
+    const LiLayout L = li_layout(batch, nx, ny, ox, oy);
     zc* ay = reinterpret_cast<zc*>(ws);
     zc* ax = ay + L.ay;
     zc* twy = ax + L.ax;
@@ -290,8 +291,9 @@ int convmat_li_t(int cplx, const void* grid, int batch, int nx, int ny, int ox, 
 using namespace trx;
 
 extern "C" size_t trx_convmat_li_ws_bytes(int dtype, int batch, int nx, int ny, int ox, int oy) {
+    (void)dtype;                     // every buffer is complex128 and the row chunk is the same for both dtypes
     if (batch <= 0 || ox < 0 || oy < 0 || nx <= 0 || ny <= 0) return 0;
-    const LiLayout L = li_layout(dtype, batch, nx, ny, ox, oy);
+    const LiLayout L = li_layout(batch, nx, ny, ox, oy);
     return sizeof(zc) * (size_t)(L.ay + L.ax + L.wy_tw + L.wx_tw + L.F + L.G + L.U);
 }
 
@@ -304,6 +306,6 @@ extern "C" int trx_convmat_li(int dtype, int grid_is_complex, const void* grid, 
     if ((size_t)16 * 2 * (size_t)(nx > ny ? nx : ny) > 64 * 1024) return TRX_ERR_UNSUPPORTED;
     if (toeplitz_lds_bytes(2 * (ox > oy ? ox : oy) + 1) > LI_LDS_MAX) return TRX_ERR_UNSUPPORTED;      // 2o+1 <= 99
     hipStream_t s = trx::api_stream(stream);
-    if (dtype == TRX_C64) return convmat_li_t<float>(grid_is_complex, grid, batch, nx, ny, ox, oy, Ex, Ey, Ux, Uy, info, ws, dtype, s);
-    return convmat_li_t<double>(grid_is_complex, grid, batch, nx, ny, ox, oy, Ex, Ey, Ux, Uy, info, ws, dtype, s);
+    if (dtype == TRX_C64) return convmat_li_t<float>(grid_is_complex, grid, batch, nx, ny, ox, oy, Ex, Ey, Ux, Uy, info, ws, s);
+    return convmat_li_t<double>(grid_is_complex, grid, batch, nx, ny, ox, oy, Ex, Ey, Ux, Uy, info, ws, s);
 }
