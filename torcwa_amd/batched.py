@@ -17,18 +17,14 @@ from .engine import Engine, default_engine
 from . import autograd_ops as ag
 from . import lattice as _lat
 from . import symmetry as _sym
+from .blockdiag import BlockDiag2, _halfspace_V, _kz_branch, _star_bd
 from .flux import FluxMixin
+from .readout import PI_REF, ReadoutMixin  # noqa: F401  (PI_REF: part of this module's interface)
+from .sector import SectorMixin
+from .swept import SweptMixin
 from .torch_eig import Eig
 from .volume import VolumeMixin
 
-# torcwa/rcwa.py:5 -- the reference's pi (typo in the 9th decimal) is part of its observable behaviour
-PI_REF = 3.141592652589793
-
-_DIRS = {"f": "forward", "forward": "forward", "b": "backward", "backward": "backward"}
-_PORTS = {"t": "transmission", "transmission": "transmission", "r": "reflection", "reflection": "reflection"}
-_SBLOCK = {("forward", "transmission"): 0, ("forward", "reflection"): 1, ("backward", "reflection"): 2, ("backward", "transmission"): 3}
-# (numerator side, denominator side) of the power normalisation for S[k]            rcwa.py:377-388
-_KZ_SIDES = {0: ("out", "in"), 1: ("in", "in"), 2: ("out", "out"), 3: ("in", "out")}
 FOURIER_RULES = ("laurent", "li", "normal")
 # fourier_rule="normal": default width (grid cells) of the Gaussian that smooths the structure tensor of a grid into the normal-vector field
 # (include/trx.h: trx_normal_field); chosen by the CPU study in profiles/normal_vector.txt
@@ -41,56 +37,37 @@ NV_SIGMA_DEFAULT = 6.0
 # patterned eps (mu); the normal-vector rule: the tensor exx, exy, eyy.
 Medium = namedtuple("Medium", "E Einv M Minv eps_s mu_s exx exy eyy mx my")
 
+# The per-layer record: every one of these attributes is a list with one entry per layer (None where a layer has no such thing), and
+# BatchedRCWA._push_layer is the one place that appends to them.  flux.py, volume.py, fields.py and rcwa.py index them by layer.
+#   thickness [B] (None: the swept layer, see _swept["d"]); eps_conv, mu_conv: Laurent's matrices; eps_grid, mu_grid (keep_coupling): the eps / mu
+#   handed to add_layer, by reference (a grid) or as the per-point scalar [B] (absorption_by_region); eps_conv_x / _y (fourier_rule="li" with
+#   keep_coupling): Li's Ex, Ey; eps_conv_xx / _xy / _yy (fourier_rule="normal" with keep_coupling): the tensor Exx, Exy (= Eyx), Eyy;
+#   symmetry_residual: resid [B] of trx_sym_fold (the discarded part of T^H A T relative to max |A|); _sector_layers (symmetry_sector):
+#   dict(P=[P_k], Q=[Q_k]) of a patterned layer
+_CONV_FIELDS = ("eps_conv", "eps_conv_x", "eps_conv_y", "eps_conv_xx", "eps_conv_xy", "eps_conv_yy")     # what a folded layer drops
+_LAYER_FIELDS = ("thickness", "mu_conv", "eps_grid", "mu_grid", "P", "Q", "kz_norm", "E_eigvec", "H_eigvec", "Cplus", "Cminus",
+                 "layer_S11", "layer_S21", "symmetry_residual", "_sector_layers") + _CONV_FIELDS
+
 
 def check_fourier_rule(rule):
     if rule not in FOURIER_RULES:
         raise ValueError(f"fourier_rule must be one of {FOURIER_RULES}, got {rule!r}")
 
 
-class BlockDiag2:
-    """2x2 block matrix whose four N x N blocks are diagonal (Vf, Vi, Vo, Sin, Sout all have this form,
-    rcwa.py:1143-1181): stored as four [B,N] diagonals, O(N) algebra instead of dense n^3."""
-
-    def __init__(self, d11, d12, d21, d22):
-        self.d = (d11, d12, d21, d22)
-
-    def __add__(self, o):
-        return BlockDiag2(*[a + b for a, b in zip(self.d, o.d)])
-
-    def __sub__(self, o):
-        return BlockDiag2(*[a - b for a, b in zip(self.d, o.d)])
-
-    def __neg__(self):
-        return BlockDiag2(*[-a for a in self.d])
-
-    def scale(self, s):
-        return BlockDiag2(*[s * a for a in self.d])
-
-    def __matmul__(self, o):
-        a, b, c, d = self.d
-        e, f, g, h = o.d
-        return BlockDiag2(a * e + b * g, a * f + b * h, c * e + d * g, c * f + d * h)
-
-    def inv(self):
-        a, b, c, d = self.d
-        det = a * d - b * c
-        return BlockDiag2(d / det, -b / det, -c / det, a / det)
-
-    def dense(self):
-        a, b, c, d = self.d
-        top = torch.cat((torch.diag_embed(a), torch.diag_embed(b)), dim=2)
-        bot = torch.cat((torch.diag_embed(c), torch.diag_embed(d)), dim=2)
-        return torch.cat((top, bot), dim=1)
+def _propagate_coupling(mm, Cm, Cn, X1, X2, Y1, Y2):
+    """The coupling lists of Sm * Sn (rcwa.py:1298-1304) from the factors X, Y of the star product: the lists Cm of the left operand take
+    Y1, Y2, the lists Cn of the right operand X1, X2 (an operand without lists: [[], []], and its factors are not read).  mm: the product."""
+    C = [[], []]
+    for cf, cb in zip(*Cm):
+        C[0].append(cf + mm(cb, Y1))
+        C[1].append(mm(cb, Y2))
+    for cf, cb in zip(*Cn):
+        C[0].append(mm(cf, X1))
+        C[1].append(cb + mm(cf, X2))
+    return C
 
 
-def _halfspace_V(kx, ky, epsmu):
-    """E->H map of a homogeneous half space, eps*mu = epsmu ([B] or scalar)        rcwa.py:1143-1147"""
-    kz = torch.sqrt(epsmu - kx ** 2 - ky ** 2)
-    kz = torch.where(torch.imag(kz) < 0, torch.conj(kz), kz)
-    return BlockDiag2(-ky * kx / kz, -kz - ky ** 2 / kz, kz + kx ** 2 / kz, kx * ky / kz)
-
-
-class BatchedRCWA(FluxMixin, VolumeMixin):
+class BatchedRCWA(FluxMixin, VolumeMixin, ReadoutMixin, SectorMixin, SweptMixin):
     def __init__(self, freq, order, L, *, batch=None, dtype=torch.complex64, device=None, stable_eig_grad=True,
                  avoid_Pinv_instability=False, max_Pinv_instability=0.005, precision="high", engine=None,
                  keep_coupling=True, fold_layers=False, eig_route="auto", route_hint=None, fourier_rule="laurent", nv_sigma=NV_SIGMA_DEFAULT,
@@ -104,7 +81,6 @@ class BatchedRCWA(FluxMixin, VolumeMixin):
         _sym.check_symmetry(symmetry)
         self.symmetry = symmetry
         self.symmetry_tol = float(symmetry_tol)
-        self.symmetry_residual = []      # per layer: resid [B] of trx_sym_fold (the discarded part of T^H A T relative to max |A|), or None
         self._sym_plans = {}
         # symmetry_grad=True (opt-in): a differentiable stack folds its eigenproblems too (SymFoldFn -> Eig per block size -> SymUnfoldFn).
         # The fold drops the part of A outside the diagonal blocks, so the eigen-part of the gradient is the one of the mirror-constrained
@@ -113,26 +89,12 @@ class BatchedRCWA(FluxMixin, VolumeMixin):
         self.symmetry_grad = bool(symmetry_grad)
         if self.symmetry_grad and symmetry is None:
             raise ValueError('symmetry_grad=True needs symmetry="x" | "y" | "xy"')
-        # symmetry_sector=True (opt-in; needs symmetry=): the caller states that the WHOLE stack shares the mirrors.  The global S-matrix is then
-        # block diagonal in the mirror basis, and solve_S_parameters solves -- eigenproblem, layer S-matrices, star products -- only the sectors
-        # the requested columns touch (one of about n / 4 for an x- or y-polarised (0, 0) order under "xy").  A patterned layer keeps the folded
-        # P_k, Q_k of every block (include/trx.h: trx_sym_fold_pair) instead of P, Q, A and its modes; there is no global S-matrix, so
-        # everything that reads one is refused.  symmetry_residual is None for such layers: the grid check with
-        # symmetry_tol is the guard.  False: today's paths, untouched.
+        # symmetry_sector=True (opt-in; needs symmetry=): only the mirror sectors a read-out touches are solved (sector.py).  False: the
+        # paths below.
         self.symmetry_sector = bool(symmetry_sector)
         if self.symmetry_sector:
-            if symmetry is None:
-                raise ValueError('symmetry_sector=True needs symmetry="x" | "y" | "xy"')
-            if keep_coupling:
-                raise ValueError("symmetry_sector=True needs keep_coupling=False: the coupling matrices of a stack live in the original basis, "
-                                 "and a sector solve keeps none (the drop-in class rcwa always keeps them)")
-            if avoid_Pinv_instability is True:
-                raise ValueError("symmetry_sector=True is not available with avoid_Pinv_instability=True (a sector takes V = Q W Kz^-1 only)")
-            if self.symmetry_grad:
-                raise ValueError("symmetry_sector=True is not available on a differentiable stack (symmetry_grad=True): the adjoint of the "
-                                 "sector cascade is not implemented")
+            self._check_sector(keep_coupling, avoid_Pinv_instability)
         self._sector_centres = None      # (cx, nx, cy, ny) of the first patterned layer: the one plan of the whole stack
-        self._sector_layers = []         # per layer: dict(P=[P_k], Q=[Q_k]) of a patterned layer, None for a homogeneous one
         self._sector_layer_S = {}        # (layer, block) -> [S11, S21] of the sector
         self._sector_S = {}              # block -> the sector of the whole stack's S-matrix, [S11, S21, S12, S22]
         # fourier_rule="li" needs the rectangular order box on a rectangular lattice (ValueError otherwise, see the order / lattice below).
@@ -170,12 +132,13 @@ class BatchedRCWA(FluxMixin, VolumeMixin):
         self.fold_layers = bool(fold_layers) and not keep_coupling
         self._running = None
         self._n_folded = 0            # layers 0 .. _n_folded-1 live in _running; the rest are stored layers
-        # add_layer(..., swept=True): the one layer whose thickness is a sweep axis [B, T].  It keeps its modes W, kz, V, forms no layer S-matrix
-        # and is not folded; the layers after it fold into a running product of their own (fold_layers).  None: today's paths, untouched.
+        # add_layer(..., swept=True): the one layer whose thickness is a sweep axis [B, T] (swept.py).  None: no such layer.
         self._swept = None            # dict(index, d [B,T])
-        self._right_running = None
+        self._right_running = None    # the layers right of the swept one fold into a running product of their own
         self._n_right_folded = 0
-        self.thickness_chunk = None   # thicknesses per library call of a swept solve (None: as many as the free HBM holds, sweep.auto_thickness_chunk)
+        self.thickness_chunk = None   # thicknesses per library call of a swept solve (None: as many as the free HBM holds, memory.auto_thickness_chunk)
+        self._diff = False            # a layer so far went through the differentiable primitives
+        self._zero_layer_S = False    # the last cascade was the one of no layer and no half-space (rcwa.py:187-188)
 
         if batch is None:
             batch = freq.numel() if (torch.is_tensor(freq) and freq.dim() > 0) else (len(freq) if isinstance(freq, (list, tuple)) else 1)
@@ -230,17 +193,8 @@ class BatchedRCWA(FluxMixin, VolumeMixin):
         self.eps_in, self.mu_in, self.eps_out, self.mu_out = one, one.clone(), one.clone(), one.clone()
         self.has_in = self.has_out = False
         self.layer_N = 0
-        self.thickness = []
-        self.eps_conv, self.mu_conv = [], []
-        # keep_coupling: the eps / mu handed to add_layer, by reference (a grid) or as the per-point scalar [B] (absorption_by_region)
-        self.eps_grid, self.mu_grid = [], []
-        self.eps_conv_x, self.eps_conv_y = [], []      # fourier_rule="li" with keep_coupling: Ex, Ey per layer (None: homogeneous / folded)
-        # fourier_rule="normal" with keep_coupling: Exx, Exy (= Eyx), Eyy per layer (None: homogeneous eps / folded)
-        self.eps_conv_xx, self.eps_conv_xy, self.eps_conv_yy = [], [], []
-        self.P, self.Q = [], []
-        self.kz_norm, self.E_eigvec, self.H_eigvec = [], [], []
-        self.Cplus, self.Cminus = [], []
-        self.layer_S11, self.layer_S21 = [], []
+        for name in _LAYER_FIELDS:
+            setattr(self, name, [])
 
     # ---- helpers -----------------------------------------------------------------------------------------
     def _bvec(self, v, dtype=None):
@@ -257,6 +211,19 @@ class BatchedRCWA(FluxMixin, VolumeMixin):
     @property
     def n(self):
         return 2 * self.order_N
+
+    @staticmethod
+    def _requires_grad(*values):
+        return torch.is_grad_enabled() and any(torch.is_tensor(v) and v.requires_grad for v in values)
+
+    def _push_layer(self, **fields):
+        """Append one layer to every per-layer list: fields[name] where given, None elsewhere."""
+        unknown = set(fields) - set(_LAYER_FIELDS)
+        if unknown:
+            raise KeyError(f"not a per-layer attribute: {sorted(unknown)}")
+        for name in _LAYER_FIELDS:
+            getattr(self, name).append(fields.get(name))
+        self.layer_N += 1
 
     # ---- a2 / a3 -----------------------------------------------------------------------------------------
     def add_input_layer(self, eps=1., mu=1.):                                           # rcwa.py:95-107
@@ -330,14 +297,7 @@ class BatchedRCWA(FluxMixin, VolumeMixin):
         if self.symmetry_sector:
             return self._add_layer_sector(thickness, eps, mu, normal_field, swept)
         if swept:
-            if self._swept is not None:
-                raise ValueError(f"add_layer(swept=True): layer {self._swept['index']} is already swept; one swept layer per solver "
-                                 "(two thickness axes would need a K per pair of thicknesses)")
-            if self.keep_coupling:
-                raise ValueError("add_layer(swept=True) needs keep_coupling=False: the coupling matrices of a stack depend on the thickness, "
-                                 "and a swept solve keeps none")
-            if self.avoid_Pinv_instability:
-                raise ValueError("add_layer(swept=True) is not available with avoid_Pinv_instability=True (the swept layer takes V = P^-1 W Kz only)")
+            self._check_swept()
         eps_h, mu_h = self._is_homogeneous(eps), self._is_homogeneous(mu)
         if normal_field is not None and self.fourier_rule != "normal":
             raise ValueError('add_layer(normal_field=...) needs fourier_rule="normal"')
@@ -345,51 +305,29 @@ class BatchedRCWA(FluxMixin, VolumeMixin):
             raise ValueError("add_layer(normal_field=...) needs a patterned eps grid")
         eye = torch.eye(N, dtype=cdt, device=self._device)
         # differentiable path (Examples 4-6): every O(n^3) primitive is an autograd.Function over the same HIP kernels
-        diff = torch.is_grad_enabled() and any(torch.is_tensor(v) and v.requires_grad for v in
-                                               (thickness, eps, mu, self.freq, self.Kx_norm_dn, self.Ky_norm_dn))
-        self._diff = getattr(self, "_diff", False) or diff
-        if (swept or self._swept is not None) and self._diff:
-            raise ValueError("swept=True is not available on a differentiable stack (a tensor of this layer or another one requires grad): "
-                             "the adjoint of the thickness sweep is not implemented")
+        diff = self._requires_grad(thickness, eps, mu, self.freq, self.Kx_norm_dn, self.Ky_norm_dn)
+        self._diff = self._diff or diff
+        self._refuse_swept_diff(swept)
         if self.symmetry is not None:
             if self._diff and not self.symmetry_grad:
                 raise ValueError("symmetry= is not available on a differentiable stack (a tensor of this layer or an earlier one requires grad): "
                                  "the adjoint of the folded eigenproblem is not implemented for a raw per-pixel gradient; symmetry_grad=True "
                                  "opts in to the gradient of the mirror-constrained problem")
-            if normal_field is not None:
-                raise ValueError("symmetry= cannot be combined with add_layer(normal_field=...): a caller-supplied field is not checked for the mirror; "
-                                 "let the field be derived from the grid")
+            self._refuse_normal_field(normal_field)
         if eps_h and mu_h and not diff and not self.keep_coupling and not swept:
             self._add_homogeneous_layer_bd(thickness, self._bvec(eps), self._bvec(mu))
-            self.symmetry_residual.append(None)
             self._fold_last_layer()
             return
         fac, plan = self._factorise(eps, mu, eps_h, mu_h, normal_field, diff, eye)
         keep = self.keep_coupling
-        eps_s, mu_s = fac.eps_s, fac.mu_s
-        self.eps_conv.append(fac.E)
-        self.mu_conv.append(fac.M)
-        self.eps_grid.append((self._bvec(eps) if eps_h else eps) if keep else None)
-        self.mu_grid.append((self._bvec(mu) if mu_h else mu) if keep else None)
+        E, mu_s = fac.E, fac.mu_s          # homogeneous mu: V = P^-1 W Kz from the rank-N structure of P (trx_hmodes)
         keep_li = keep and fac.exy is None and fac.exx is not fac.E          # Li's Ex, Ey of a patterned eps
-        self.eps_conv_x.append(fac.exx if keep_li else None)
-        self.eps_conv_y.append(fac.eyy if keep_li else None)
         keep_nv = keep and fac.exy is not None
-        self.eps_conv_xx.append(fac.exx if keep_nv else None)
-        self.eps_conv_xy.append(fac.exy if keep_nv else None)
-        self.eps_conv_yy.append(fac.eyy if keep_nv else None)
-        self.layer_N += 1
-        if swept:
-            d = torch.as_tensor(thickness, dtype=self._rdtype, device=self._device)
-            if d.dim() == 1:
-                d = d[None, :].expand(B, -1)
-            if d.dim() != 2 or d.shape[0] != B:
-                raise ValueError(f"add_layer(swept=True): thickness must be [T] or [{B}, T], got {list(d.shape)}")
-            self._swept = dict(index=self.layer_N - 1, d=d.contiguous())
-            self.thickness.append(None)          # no single thickness: see _swept["d"]
-        else:
-            d = self._bvec(thickness, self._rdtype)
-            self.thickness.append(d)
+        rec = dict(eps_conv=E, mu_conv=fac.M,
+                   eps_grid=(self._bvec(eps) if eps_h else eps) if keep else None, mu_grid=(self._bvec(mu) if mu_h else mu) if keep else None,
+                   eps_conv_x=fac.exx if keep_li else None, eps_conv_y=fac.eyy if keep_li else None,
+                   eps_conv_xx=fac.exx if keep_nv else None, eps_conv_xy=fac.exy if keep_nv else None, eps_conv_yy=fac.eyy if keep_nv else None)
+        d = self._swept_thickness(thickness) if swept else self._bvec(thickness, self._rdtype)
         kxd, kyd = self.Kx_norm_dn, self.Ky_norm_dn
         inv = (lambda A: ag.InverseFn.apply(A, eng)) if diff else eng.inverse
         if fac.Einv is None:
@@ -397,10 +335,10 @@ class BatchedRCWA(FluxMixin, VolumeMixin):
         if fac.Minv is None and fac.M is not None:
             fac = fac._replace(Minv=inv(fac.M))
         P, Q = self._pq(fac, diff)
+        resid = None
         if eps_h and mu_h:                                                              # rcwa.py:1206-1222
             W = torch.eye(2 * N, dtype=cdt, device=self._device).expand(B, -1, -1).contiguous()
-            kz = torch.sqrt((eps_s * mu_s)[:, None] - kxd ** 2 - kyd ** 2)
-            kz = torch.where(torch.imag(kz) < 0, torch.conj(kz), kz)
+            kz = _kz_branch(torch.sqrt((fac.eps_s * mu_s)[:, None] - kxd ** 2 - kyd ** 2))
             kz = torch.cat((kz, kz), dim=1)
         else:                                                                           # rcwa.py:1224-1242
             if diff:
@@ -425,22 +363,23 @@ class BatchedRCWA(FluxMixin, VolumeMixin):
                 else:
                     lam, W, resid = self._eig_folded(A, plan, steps)
                 del A
-            kz = torch.sqrt(lam)
-            kz = torch.where(torch.imag(kz) < 0, -kz, kz)                               # rcwa.py:1241
-        self.symmetry_residual.append(resid if plan is not None else None)
-        self.P.append(P)
-        self.Q.append(Q)
-        self.kz_norm.append(kz)
-        self.E_eigvec.append(W)
-        self._mu_scalar = mu_s                         # homogeneous mu: V = P^-1 W Kz from the rank-N structure of P (trx_hmodes)
+            kz = _kz_branch(torch.sqrt(lam), negate=True)                               # rcwa.py:1241
         if swept:
-            self._keep_swept_modes()
+            V = self._keep_swept_modes(P, W, kz, mu_s, E)
+            self._push_layer(P=P, Q=Q, kz_norm=kz, E_eigvec=W, H_eigvec=V, symmetry_residual=resid, **rec)
+            self._swept = dict(index=self.layer_N - 1, d=d)
+            if self.fold_layers:              # as a folded layer: the matrices the modes came from are not read again
+                self._drop_layer_matrices(self.layer_N - 1, modes=True)
             return
-        if diff:
-            self._solve_layer_smatrix_diff()
-        else:
-            self._solve_layer_smatrix()
+        S11, S21, V, cp, cm, W_kept = (self._solve_layer_smatrix_diff if diff else self._solve_layer_smatrix)(P, Q, W, kz, d, mu_s, E)
+        self._push_layer(thickness=d, P=P, Q=Q, kz_norm=kz, E_eigvec=W_kept, H_eigvec=V, Cplus=cp, Cminus=cm, layer_S11=S11, layer_S21=S21,
+                         symmetry_residual=resid, **rec)
         self._fold_last_layer()
+
+    def _refuse_normal_field(self, normal_field):
+        if normal_field is not None:
+            raise ValueError("symmetry= cannot be combined with add_layer(normal_field=...): a caller-supplied field is not checked for the mirror; "
+                             "let the field be derived from the grid")
 
     def _grid(self, v):
         """eps / mu grid [nx, ny] or [B, nx, ny] -> contiguous [B, nx, ny] on the device."""
@@ -544,16 +483,8 @@ class BatchedRCWA(FluxMixin, VolumeMixin):
 
     def _drop_layer_matrices(self, i, modes=False):
         """The convolution matrices of a folded layer are not read again; modes: nor are the P, Q its modes came from (the swept layer)."""
-        self.eps_conv[i] = None
-        self.eps_conv_x[i] = self.eps_conv_y[i] = None
-        self.eps_conv_xx[i] = self.eps_conv_xy[i] = self.eps_conv_yy[i] = None
-        if modes:
-            self.P[i] = self.Q[i] = None
-
-    @staticmethod
-    def _append_none(*lists):
-        for lst in lists:
-            lst.append(None)
+        for name in _CONV_FIELDS + (("P", "Q") if modes else ()):
+            getattr(self, name)[i] = None
 
     def _pack_bd(self, S):
         """Four BlockDiag2 blocks -> [4,4,B,N] diagonals in the compute dtype, as the library takes a block-diagonal S-matrix."""
@@ -563,92 +494,25 @@ class BatchedRCWA(FluxMixin, VolumeMixin):
         """Streaming cascade: fold the layer just added into the running star product and drop it.  Decided PER LAYER: a layer is folded
         only while the stack so far is a plain (non-differentiable) prefix 0 .. i-1 that has itself been folded; from the first
         differentiable layer on, layers stay stored and solve_global_smatrix continues the cascade from the folded prefix over them
-        (a global early return here used to leave such layers out of the cascade altogether)."""
+        (a global early return here used to leave such layers out of the cascade altogether).  Right of the swept layer: the same
+        streaming cascade into a product of its own."""
         i = self.layer_N - 1
-        sw = self._swept
-        if sw is not None and i > sw["index"]:
-            # right of the swept layer: the same streaming cascade into a product of its own
-            if self.fold_layers and self._n_right_folded == i - sw["index"] - 1:
-                S = self._layer_S(i)
-                self._right_running = S if self._right_running is None else self._star(self._right_running, S, [[], []], [[], []])[0]
-                self.layer_S11[i] = self.layer_S21[i] = None
-                self._drop_layer_matrices(i)
-                self._n_right_folded += 1
-            return
-        if not self.fold_layers or getattr(self, "_diff", False) or self._n_folded != i:
-            return
-        S = self._layer_S(i)
-        if self._running is None:
-            self._running = S
+        right = self._swept is not None and i > self._swept["index"]
+        if right:
+            ready = self._n_right_folded == i - self._swept["index"] - 1
         else:
-            self._running, _ = self._star(self._running, S, [[], []], [[], []])
+            ready = not self._diff and self._n_folded == i
+        if not (self.fold_layers and ready):
+            return
+        S, run = self._layer_S(i), self._right_running if right else self._running
+        if run is not None:
+            S = self._star(run, S, [[], []], [[], []])[0]
+        if right:
+            self._right_running, self._n_right_folded = S, self._n_right_folded + 1
+        else:
+            self._running, self._n_folded = S, i + 1
         self.layer_S11[i] = self.layer_S21[i] = None
         self._drop_layer_matrices(i)
-        self._n_folded = i + 1
-
-    def _keep_swept_modes(self):
-        """The swept layer: V = P^-1 W Kz (rcwa.py:1248, 1264; trx_hmodes for a homogeneous mu) next to W and kz; no layer S-matrix."""
-        eng = self.engine
-        W, kz = self.E_eigvec[-1], self.kz_norm[-1]
-        if self._mu_scalar is not None:
-            V = eng.hmodes(self.eps_conv[-1], self._mu_scalar, self.Kx_norm_dn, self.Ky_norm_dn, W, kz)
-        else:
-            V = eng.solve(self.P[-1], W * kz[:, None, :])
-        self.H_eigvec.append(V)
-        self._append_none(self.layer_S11, self.layer_S21, self.Cplus, self.Cminus)
-        if self.fold_layers:              # as a folded layer: the matrices the modes came from are not read again
-            self._drop_layer_matrices(self.layer_N - 1, modes=True)
-
-    def _swept_sides(self):
-        """(Lft, Rgt): everything left / right of the swept layer as one S-matrix each -- None (nothing there), a list of four BlockDiag2
-        (half-space and homogeneous layers only) or of four [B,n,n] tensors."""
-        i = self._swept["index"]
-        none = [[], []]
-        Lft = None
-        first = 0
-        if self._n_folded > 0:
-            Lft, first = self._running, self._n_folded
-        for j in range(first, i):
-            Lft = self._layer_S(j) if Lft is None else self._star(Lft, self._layer_S(j), none, none)[0]
-        if self.has_in:
-            Lft = self._Sin if Lft is None else self._star(self._Sin, Lft, none, none)[0]
-        Rgt = None
-        first = i + 1
-        if self._n_right_folded > 0:
-            Rgt, first = self._right_running, i + 1 + self._n_right_folded
-        for j in range(first, self.layer_N):
-            Rgt = self._layer_S(j) if Rgt is None else self._star(Rgt, self._layer_S(j), none, none)[0]
-        if self.has_out:
-            Rgt = self._Sout if Rgt is None else self._star(Rgt, self._Sout, none, none)[0]
-        return Lft, Rgt
-
-    def _solve_swept(self, orders, direction, port, polarization, ref_order, power_norm, evanscent):
-        """solve_S_parameters of a solver with a swept layer: [B, T, len(orders)]."""
-        orders, polarization, oi, ri, k = self._sparam_args(orders, direction, port, polarization, ref_order)
-        cols = self._sparam_columns(ri, polarization)
-        sw = self._swept
-        i = sw["index"]
-        ops = []
-        for S in self._swept_sides():
-            if S is not None and self._is_bd(S):
-                S = self._pack_bd(S)
-            ops.append(S)
-        vfinv = torch.stack(self._Vfinv.d, dim=0).to(self._cdtype).contiguous()                                         # [4,B,N]
-        prep = self.engine.thickness_prepare(self.E_eigvec[i], self.H_eigvec[i], vfinv, ops[0], ops[1], 0 if k < 2 else 1, cols)
-        phase = torch.exp(1j * (self.omega[:, None] * sw["d"])[:, :, None] * self.kz_norm[i][:, None, :])               # [B, T, n]   rcwa.py:1246
-        chunk = self.thickness_chunk
-        if not chunk:
-            from .sweep import auto_thickness_chunk
-            chunk = auto_thickness_chunk(self.B, sw["d"].shape[1], self.n, len(cols), self._cdtype, self._device)
-        out = self.engine.thickness_columns(prep, phase, 0 if k in (0, 3) else 1, chunk=chunk)                          # [B, T, n, m]
-        vals = [self._sparam_values(lambda c, t=t: out[:, t, :, cols.index(c)], k, oi, ri, polarization, power_norm, evanscent)
-                for t in range(out.shape[1])]
-        return torch.stack(vals, dim=1)
-
-    def _refuse_swept(self, what):
-        if self._swept is not None:
-            raise ValueError(f"{what} is not available on a solver with a swept layer (add_layer(..., swept=True)): there is no single stack to "
-                             "solve; solve_S_parameters(...) returns the S-parameters of every thickness")
 
     def _add_homogeneous_layer_bd(self, thickness, eps_s, mu_s):
         """Homogeneous layer without field bookkeeping (keep_coupling=False): every operator of rcwa.py:1206-1222 and 1244-1281
@@ -658,23 +522,17 @@ class BatchedRCWA(FluxMixin, VolumeMixin):
         kxd, kyd = self.Kx_norm_dn, self.Ky_norm_dn
         d = self._bvec(thickness, self._rdtype)
         epsmu = (eps_s * mu_s)[:, None]
-        kz = torch.sqrt(epsmu - kxd ** 2 - kyd ** 2)
-        kz = torch.where(torch.imag(kz) < 0, torch.conj(kz), kz)                        # rcwa.py:1218
+        kz = _kz_branch(torch.sqrt(epsmu - kxd ** 2 - kyd ** 2))                        # rcwa.py:1218
         x = torch.exp(1j * (self.omega * d)[:, None] * kz)                              # rcwa.py:1246, [B,N] (same for both field components)
         V = _halfspace_V(kxd, kyd, epsmu).scale(1 / mu_s[:, None])                      # Q Kz^-1 = P^-1 Kz
-        one, zero = torch.ones_like(kz), torch.zeros_like(kz)
-        I = BlockDiag2(one, zero, zero, one)
+        I = BlockDiag2.identity_like(kz)
         F = self._Vfinv @ V
         A_, B_ = I + F, (I - F).scale(x)
         Tip, Tim = (A_ + B_).inv(), (A_ - B_).inv()
         cp, cm = Tip + Tim, Tip - Tim
-        self.layer_S11.append(cp.scale(x) + cm)                                         # rcwa.py:1276 with W = I
-        self.layer_S21.append(cp + cm.scale(x) - I)                                     # rcwa.py:1277
-        self.layer_N += 1
-        self.thickness.append(d)
-        self.kz_norm.append(torch.cat((kz, kz), dim=1))
-        self._append_none(self.eps_conv, self.mu_conv, self.eps_grid, self.mu_grid, self.eps_conv_x, self.eps_conv_y, self.eps_conv_xx, self.eps_conv_xy,
-                          self.eps_conv_yy, self.P, self.Q, self.E_eigvec, self.H_eigvec, self.Cplus, self.Cminus)
+        self._push_layer(thickness=d, kz_norm=torch.cat((kz, kz), dim=1),
+                         layer_S11=cp.scale(x) + cm,                                    # rcwa.py:1276 with W = I
+                         layer_S21=cp + cm.scale(x) - I)                                # rcwa.py:1277
 
     def _nv_spacing(self, g):
         """Grid spacings (hx, hy) of a [B, nx, ny] grid over the unit cell: they orient the gradient of the normal-vector field.  On the
@@ -728,16 +586,16 @@ class BatchedRCWA(FluxMixin, VolumeMixin):
             Q = Q + torch.cat((torch.cat((-Exy, torch.zeros_like(Exy)), dim=2), torch.cat((torch.zeros_like(Exy), Exy), dim=2)), dim=1)
         return P, Q
 
-    def _solve_layer_smatrix_diff(self):
-        """Layer S-matrix (rcwa.py:1244-1281) from differentiable primitives; same lean algebra as trx_layer_smatrix."""
-        eng, N, n = self.engine, self.order_N, self.n
-        P, W, kz, d = self.P[-1], self.E_eigvec[-1], self.kz_norm[-1], self.thickness[-1]
+    def _solve_layer_smatrix_diff(self, P, Q, W, kz, d, mu_s, E):
+        """Layer S-matrix (rcwa.py:1244-1281) from differentiable primitives; same lean algebra as trx_layer_smatrix.  Arguments and
+        return value as _solve_layer_smatrix (mu_s and E are not read: this path always solves with P)."""
+        eng, n = self.engine, self.n
         X = torch.exp(1j * (self.omega * d)[:, None] * kz)                              # [B, n]
         WKz = W * kz[:, None, :]
         bad = None
         if self.avoid_Pinv_instability:                                                 # rcwa.py:1249-1262 (metrics are detached diagnostics)
             with torch.no_grad():
-                Pd, Qd = P.detach(), self.Q[-1].detach()
+                Pd, Qd = P.detach(), Q.detach()
                 I = torch.eye(n, dtype=self._cdtype, device=self._device)
                 Pinv = eng.inverse(Pd)
                 ins = torch.maximum(torch.amax(torch.abs(eng.gemm(Pd, Pinv) - I), dim=(1, 2)),
@@ -755,21 +613,16 @@ class BatchedRCWA(FluxMixin, VolumeMixin):
             # (0 * NaN in SolveFn.backward would poison the gradient of every point): those points solve with the identity instead
             sel = bad[:, None, None]
             I = torch.eye(n, dtype=self._cdtype, device=self._device)
-            V = torch.where(sel, ag.GemmFn.apply(self.Q[-1], (W / kz[:, None, :]).contiguous(), eng),
+            V = torch.where(sel, ag.GemmFn.apply(Q, (W / kz[:, None, :]).contiguous(), eng),
                             ag.SolveFn.apply(torch.where(sel, I, P), WKz, eng))
-        p11, p12, p21, p22 = [t.to(self._cdtype)[:, :, None] for t in self._Vfinv.d]
-        F = torch.cat((p11 * V[:, :N] + p12 * V[:, N:], p21 * V[:, :N] + p22 * V[:, N:]), dim=1)    # Vf^-1 V
+        F = self._Vfinv.apply(V)                                                        # Vf^-1 V
         A_, B_ = W + F, (W - F) * X[:, None, :]
         Tip, Tim = ag.InverseFn.apply(A_ + B_, eng), ag.InverseFn.apply(A_ - B_, eng)
         cp, cm = Tip + Tim, Tip - Tim
         I = torch.eye(n, dtype=self._cdtype, device=self._device)
         S11 = ag.GemmFn.apply(W, X[:, :, None] * cp + cm, eng)
         S21 = ag.GemmFn.apply(W, cp + X[:, :, None] * cm, eng) - I
-        self.H_eigvec.append(V)
-        self.layer_S11.append(S11)
-        self.layer_S21.append(S21)
-        self.Cplus.append(cp)
-        self.Cminus.append(cm)
+        return S11, S21, V, cp, cm, W
 
     def _RS_prod_diff(self, Sm, Sn, Cm, Cn):
         """Star product (rcwa.py:1283-1306) from differentiable primitives (one factorisation, push-through identity)."""
@@ -781,14 +634,7 @@ class BatchedRCWA(FluxMixin, VolumeMixin):
         X1, X2 = X12[:, :, :n], X12[:, :, n:]
         Y1, Y2 = mm(Sn[1], X1), Sn[3] + mm(Sn[1], X2)
         S = [mm(Sn[0], X1), Sm[1] + mm(Sm[3], Y1), Sn[2] + mm(Sn[0], X2), mm(Sm[3], Y2)]
-        C = [[], []]
-        for m in range(len(Cm[0])):
-            C[0].append(Cm[0][m] + mm(Cm[1][m], Y1))
-            C[1].append(mm(Cm[1][m], Y2))
-        for k in range(len(Cn[0])):
-            C[0].append(mm(Cn[0][k], X1))
-            C[1].append(Cn[1][k] + mm(Cn[0][k], X2))
-        return S, C
+        return S, _propagate_coupling(mm, Cm, Cn, X1, X2, Y1, Y2)
 
     def _eig_call(self, A, refine_steps, out=None):
         """trx_eig with this solver's route policy.  "fp64" / "mixed": as named.  "auto": the library's mixed-precision route, and -- scoped to THIS
@@ -843,125 +689,6 @@ class BatchedRCWA(FluxMixin, VolumeMixin):
         lam, W = ag.SymUnfoldFn.apply(plan, eng, *[p[1] for p in pairs], *[p[0] for p in pairs])
         return lam, W, resid
 
-    # ---- sector solves (symmetry_sector=True) ------------------------------------------------------------
-    def _refuse_sector(self, what):
-        if self.symmetry_sector:
-            raise ValueError(f"{what} is not available with symmetry_sector=True: only the mirror sectors a source excites are solved, so there is "
-                             "no global S-matrix and there are no coupling matrices; solve_S_parameters(...) is the read-out of a sector solve")
-
-    def _add_layer_sector(self, thickness, eps, mu, normal_field, swept):
-        """add_layer of a sector solver: a patterned layer is factorised and its P, Q are built as always (any fourier_rule, a patterned mu),
-        then every block keeps P_k = T_k^H P T_k', Q_k = T_k'^H Q T_k and the full-size P, Q are dropped: no A, no eigen call here.  A
-        homogeneous layer keeps its block-diagonal S-matrix."""
-        eng = self.engine
-        if swept:
-            raise ValueError("add_layer(swept=True) is not available with symmetry_sector=True: the thickness sweep works on the modes of the "
-                             "original basis")
-        if normal_field is not None:
-            raise ValueError("symmetry= cannot be combined with add_layer(normal_field=...): a caller-supplied field is not checked for the mirror; "
-                             "let the field be derived from the grid")
-        if torch.is_grad_enabled() and any(torch.is_tensor(v) and v.requires_grad for v in
-                                           (thickness, eps, mu, self.freq, self.Kx_norm_dn, self.Ky_norm_dn)):
-            raise ValueError("symmetry_sector=True is not available on a differentiable stack (a tensor of this layer requires grad): the "
-                             "adjoint of the sector cascade is not implemented")
-        eps_h, mu_h = self._is_homogeneous(eps), self._is_homogeneous(mu)
-        self._sector_S = {}
-        self.symmetry_residual.append(None)
-        if eps_h and mu_h:
-            self._add_homogeneous_layer_bd(thickness, self._bvec(eps), self._bvec(mu))
-            self._sector_layers.append(None)
-            return
-        eye = torch.eye(self.order_N, dtype=self._cdtype, device=self._device)
-        fac, plan = self._factorise(eps, mu, eps_h, mu_h, None, False, eye)
-        if fac.Einv is None:
-            fac = fac._replace(Einv=eng.inverse(fac.E))
-        if fac.Minv is None:
-            fac = fac._replace(Minv=eng.inverse(fac.M))
-        P, Q = self._pq(fac, False)
-        del fac
-        opp = [_sym.opposite_block(plan.nblk, k) for k in range(plan.nblk)]
-        self._sector_layers.append(dict(P=[eng.sym_fold_pair(P, plan, k, opp[k]) for k in range(plan.nblk)],
-                                        Q=[eng.sym_fold_pair(Q, plan, opp[k], k) for k in range(plan.nblk)]))
-        del P, Q
-        self.layer_N += 1
-        self.thickness.append(self._bvec(thickness, self._rdtype))
-        self._append_none(self.eps_conv, self.mu_conv, self.eps_grid, self.mu_grid, self.eps_conv_x, self.eps_conv_y, self.eps_conv_xx, self.eps_conv_xy,
-                          self.eps_conv_yy, self.P, self.Q, self.kz_norm, self.E_eigvec, self.H_eigvec, self.Cplus, self.Cminus, self.layer_S11,
-                          self.layer_S21)
-
-    def _sector_plan(self):
-        """The one plan of the stack: that of the first patterned layer's centres; centres 0 when no layer is patterned."""
-        key = self._sector_centres if self._sector_centres is not None else (0, 1, 0, 1)
-        if key not in self._sym_plans:
-            self._sym_plans[key] = _sym.build_plan(self._mn, self.symmetry, *key)
-        return self._sym_plans[key]
-
-    def _sector_bd(self, blk, kl, kr):
-        """Dense sector block T_kl^H M T_kr of a BlockDiag2 M."""
-        return self.engine.sym_fold_pair_bd(torch.stack(blk.d, dim=0).to(self._cdtype).contiguous(), self._sector_plan(), kl, kr)
-
-    def _sector_layer(self, i, k):
-        """[S11, S21] of layer i in sector k (cached): the lean formulation of SURVEY.md section 7.2 on the folded operators, with
-        V_k = Q_k W_k Kz^-1 and the dense Vf^-1 block (k, k')."""
-        if (i, k) in self._sector_layer_S:
-            return self._sector_layer_S[(i, k)]
-        eng, rec = self.engine, self._sector_layers[i]
-        if rec is None:
-            S = [self._sector_bd(self.layer_S11[i], k, k), self._sector_bd(self.layer_S21[i], k, k)]
-        else:
-            plan = self._sector_plan()
-            A = eng.gemm(rec["P"][k], rec["Q"][k])
-            lam, W = self._eig_call(A, refine_steps=3 if self._dtype == torch.complex128 else 2)
-            del A
-            kz = torch.sqrt(lam)
-            kz = torch.where(torch.imag(kz) < 0, -kz, kz)                               # rcwa.py:1241
-            X = torch.exp(1j * (self.omega * self.thickness[i])[:, None] * kz)          # rcwa.py:1246
-            V = eng.gemm(rec["Q"][k], (W / kz[:, None, :]).contiguous())                # Q W Kz^-1, in the coordinates of block k'
-            F = eng.gemm(self._sector_bd(self._Vfinv, k, _sym.opposite_block(plan.nblk, k)), V)
-            A_, B_ = W + F, (W - F) * X[:, None, :]
-            I = torch.eye(W.shape[-1], dtype=self._cdtype, device=self._device).expand(self.B, -1, -1).contiguous()
-            Tip, Tim = eng.solve(A_ + B_, I), eng.solve(A_ - B_, I)
-            cp, cm = Tip + Tim, Tip - Tim
-            S = [eng.gemm(W, X[:, :, None] * cp + cm), eng.gemm(W, cp + X[:, :, None] * cm) - I]
-        self._sector_layer_S[(i, k)] = S
-        return S
-
-    def _sector_global(self, k):
-        """Sector k of the whole stack's S-matrix (cached): the Redheffer products of the layers' sectors and the folded half-spaces."""
-        if k in self._sector_S:
-            return self._sector_S[k]
-        eng = self.engine
-        S = None
-        for i in range(self.layer_N):
-            S11, S21 = self._sector_layer(i, k)
-            Si = [S11, S21, S21, S11]
-            S = Si if S is None else eng.redheffer(S, Si)[0]
-        if S is None:
-            nk = self._sector_plan().sizes[k]
-            I = torch.eye(nk, dtype=self._cdtype, device=self._device).expand(self.B, -1, -1).contiguous()
-            Z = torch.zeros_like(I)
-            S = [I, Z, Z.clone(), I.clone()]
-        if self.has_in:
-            S = eng.redheffer([self._sector_bd(blk, k, k) for blk in self._Sin], S)[0]
-        if self.has_out:
-            S = eng.redheffer(S, [self._sector_bd(blk, k, k) for blk in self._Sout])[0]
-        self._sector_S[k] = S
-        return S
-
-    def _solve_sector(self, orders, direction, port, polarization, ref_order, power_norm, evanscent):
-        """solve_S_parameters of a sector solver: column c of block kb of the global S-matrix is sum_k T_k S^(k)_kb T_k^H e_c over the sectors
-        that c touches; the expansion is plain indexing, O(n) per column, and a row no sector reaches is exactly 0."""
-        orders, polarization, oi, ri, kb = self._sparam_args(orders, direction, port, polarization, ref_order)
-        plan = self._sector_plan()
-        full = {}
-        for c in self._sparam_columns(ri, polarization):
-            col = torch.zeros((self.B, self.n), dtype=self._cdtype, device=self._device)
-            for k, j, w in _sym.sector_coordinates(plan, c):
-                rows, src, wts = plan.expansion(k, self._device, self._cdtype)
-                y = w * self._sector_global(k)[kb][:, :, j]
-                col[:, rows] += wts[None, :] * y[:, src]
-            full[c] = col
-        return self._sparam_values(lambda c: full[c], kb, oi, ri, polarization, power_norm, evanscent)
 
     def _is_homogeneous(self, v):
         if isinstance(v, (float, complex)):
@@ -973,14 +700,16 @@ class BatchedRCWA(FluxMixin, VolumeMixin):
         # sweep point; any other 1-D tensor is NOT homogeneous, exactly as in the reference (it then fails in the grid path like there).
         return t.dim() == 0 or (t.dim() == 1 and t.shape[0] in (1, self.B))
 
-    def _solve_layer_smatrix(self):                                                     # rcwa.py:1244-1281
+    def _solve_layer_smatrix(self, P, Q, W, kz, d, mu_s, E):                            # rcwa.py:1244-1281
+        """(S11, S21, V, c+, c-, W) of a layer of thickness d [B] from its modes W, kz and P (or Q where P is ill-conditioned:
+        avoid_Pinv_instability); with a homogeneous mu, mu_s [B], V comes from E instead (trx_hmodes; P, Q may be None then).  The W that
+        comes back is the one to store: None, like V, where the sweep drivers do not read the mode matrices again."""
         eng = self.engine
-        P, Q, W, kz, d = self.P[-1], self.Q[-1], self.E_eigvec[-1], self.kz_norm[-1], self.thickness[-1]
         phase = torch.exp(1j * (self.omega * d)[:, None] * kz)                          # rcwa.py:1246
-        vfinv = torch.stack(self._Vfinv.d, dim=0).to(self._cdtype).contiguous()         # [4,B,N]
+        vfinv = self._Vfinv.packed(self._cdtype)                                        # [4,B,N]
         if not self.avoid_Pinv_instability:
-            if self._mu_scalar is not None:                                             # rcwa.py:1264, structured (include/trx.h: trx_hmodes)
-                Vh = eng.hmodes(self.eps_conv[-1], self._mu_scalar, self.Kx_norm_dn, self.Ky_norm_dn, W, kz)
+            if mu_s is not None:                                                        # rcwa.py:1264, structured (include/trx.h: trx_hmodes)
+                Vh = eng.hmodes(E, mu_s, self.Kx_norm_dn, self.Ky_norm_dn, W, kz)
                 S11, S21, V, cp, cm = eng.layer_smatrix(None, None, W, kz, vfinv, phase, want_c=self.keep_coupling, V=Vh)
             else:
                 S11, S21, V, cp, cm = eng.layer_smatrix(P, None, W, kz, vfinv, phase, use_q=False, want_c=self.keep_coupling)
@@ -1001,67 +730,40 @@ class BatchedRCWA(FluxMixin, VolumeMixin):
                 S11, S21, V = torch.where(sel, alt[0], S11), torch.where(sel, alt[1], S21), torch.where(sel, alt[2], V)
                 if self.keep_coupling:
                     cp, cm = torch.where(sel, alt[3], cp), torch.where(sel, alt[4], cm)
-        if not self.keep_coupling and not self.avoid_Pinv_instability and self._mu_scalar is not None:
-            self.E_eigvec[-1] = None          # sweep drivers: the mode matrices are not read again (see add_layer)
-            V = None
-        self.H_eigvec.append(V)
-        self.layer_S11.append(S11)
-        self.layer_S21.append(S21)
-        self.Cplus.append(cp)
-        self.Cminus.append(cm)
+        if not self.keep_coupling and not self.avoid_Pinv_instability and mu_s is not None:
+            W = V = None                      # sweep drivers: the mode matrices are not read again (see _factorise)
+        return S11, S21, V, cp, cm, W
 
     # ---- a9 / a10 ----------------------------------------------------------------------------------------
     def _RS_prod(self, Sm, Sn, Cm, Cn):                                                 # rcwa.py:1283-1306
-        eng = self.engine
-        if getattr(self, "_diff", False):
+        if self._diff:
             return self._RS_prod_diff(Sm, Sn, Cm, Cn)
-        S, X1, X2, Y1, Y2 = eng.redheffer(Sm, Sn)
-        C = [[], []]
-        for m in range(len(Cm[0])):
-            C[0].append(Cm[0][m] + eng.gemm(Cm[1][m], Y1.contiguous()))
-            C[1].append(eng.gemm(Cm[1][m], Y2.contiguous()))
-        for k in range(len(Cn[0])):
-            C[0].append(eng.gemm(Cn[0][k], X1.contiguous()))
-            C[1].append(Cn[1][k] + eng.gemm(Cn[0][k], X2.contiguous()))
-        return S, C
+        S, X1, X2, Y1, Y2 = self.engine.redheffer(Sm, Sn)
+        return S, _propagate_coupling(self._mm_plain, Cm, Cn, X1, X2, Y1, Y2)
+
+    def _mm_plain(self, a, b):
+        return self.engine.gemm(a, b.contiguous())
 
     def _RS_halfspace(self, side, Sbd, S, C):
-        """Star product with Sin (side 0) / Sout (side 1), whose blocks are 2x2-block-diagonal: O(n^2) products with them."""
-        eng = self.engine
-        if getattr(self, "_diff", False):
+        """Star product with Sin (side 0) / Sout (side 1), whose blocks are 2x2-block-diagonal: O(n^2) products with them.  C: the lists
+        of the dense operand -- the right one for side 0 (rcwa.py:1302-1304), the left one for side 1 (rcwa.py:1298-1300)."""
+        none = [[], []]
+        Cm, Cn = (none, C) if side == 0 else (C, none)
+        if self._diff:
             dense = [blk.dense().to(self._cdtype) for blk in Sbd]
-            return self._RS_prod_diff(dense, S, [[], []], C) if side == 0 else self._RS_prod_diff(S, dense, C, [[], []])
-        bd = self._pack_bd(Sbd)
-        Sn, X1, X2, Y1, Y2 = eng.redheffer_halfspace(side, bd, S, want_xy=len(C[0]) > 0)
-        Cn = [[], []]
-        if side == 0:                       # C belongs to the right operand (rcwa.py:1302-1304)
-            for k in range(len(C[0])):
-                Cn[0].append(eng.gemm(C[0][k], X1.contiguous()))
-                Cn[1].append(C[1][k] + eng.gemm(C[0][k], X2.contiguous()))
-        else:                               # C belongs to the left operand (rcwa.py:1298-1300)
-            for m in range(len(C[0])):
-                Cn[0].append(C[0][m] + eng.gemm(C[1][m], Y1.contiguous()))
-                Cn[1].append(eng.gemm(C[1][m], Y2.contiguous()))
-        return Sn, Cn
+            return self._RS_prod_diff(dense, S, Cm, Cn) if side == 0 else self._RS_prod_diff(S, dense, Cm, Cn)
+        Sn, X1, X2, Y1, Y2 = self.engine.redheffer_halfspace(side, self._pack_bd(Sbd), S, want_xy=len(C[0]) > 0)
+        return Sn, _propagate_coupling(self._mm_plain, Cm, Cn, X1, X2, Y1, Y2)
 
     @staticmethod
     def _is_bd(S):
         return isinstance(S[0], BlockDiag2)
 
-    @staticmethod
-    def _RS_bd_bd(Sm, Sn):
-        """Star product of two block-diagonal S-matrices (rcwa.py:1287-1296), O(N)."""
-        one, zero = torch.ones_like(Sm[0].d[0]), torch.zeros_like(Sm[0].d[0])
-        I = BlockDiag2(one, zero, zero, one)
-        t1 = (I - Sm[2] @ Sn[1]).inv()
-        t2 = (I - Sn[1] @ Sm[2]).inv()
-        return [Sn[0] @ t1 @ Sm[0], Sm[1] + Sm[3] @ t2 @ Sn[1] @ Sm[0], Sn[2] + Sn[0] @ t1 @ Sm[2] @ Sn[3], Sm[3] @ t2 @ Sn[3]]
-
     def _star(self, Sm, Sn, Cm, Cn):
         """Sm * Sn for any mix of dense ([B,n,n] tensors) and block-diagonal (BlockDiag2) operands."""
         bm, bn = self._is_bd(Sm), self._is_bd(Sn)
         if bm and bn:
-            return self._RS_bd_bd(Sm, Sn), [[], []]
+            return _star_bd(Sm, Sn), [[], []]
         if bm:
             return self._RS_halfspace(0, Sm, Sn, Cn)
         if bn:
@@ -1077,37 +779,39 @@ class BatchedRCWA(FluxMixin, VolumeMixin):
             return [[], []]
         return [[torch.cat((self.Cplus[i], self.Cminus[i]), dim=1)], [torch.cat((self.Cminus[i], self.Cplus[i]), dim=1)]]
 
+    def _stored_layers(self, lo, hi):
+        """(S, C) of the stored layers lo .. hi - 1, each formed when the chain reaches it."""
+        return ((self._layer_S(i), self._layer_C(i)) for i in range(lo, hi))
+
+    def _star_chain(self, S, C, items):
+        """(S, C) * (S_1, C_1) * (S_2, C_2) ... from left to right over the (S_i, C_i) of `items`; S None: the first item starts the chain
+        (and None comes back when there is none)."""
+        for Sn, Cn in items:
+            S, C = (Sn, Cn) if S is None else self._star(S, Sn, C, Cn)
+        return S, C
+
     def _cascade(self, defer_last=False):
         """The cascade of solve_global_smatrix (rcwa.py:173-211): returns (S, C, None).  defer_last: when the LAST star product is one with a
         half-space on the plain path -- a dense running S, no coupling lists to propagate (keep_coupling=False), no differentiable layer -- it is
         not formed: (S before it, C, side) comes back, side 0 for the pending Sin * S, 1 for S * Sout (solve_S_parameters probes it)."""
         n, B = self.n, self.B
-        self._zero_layer_S = False
-        first = 1                                                                       # first stored layer still to be folded in
-        if self._n_folded > 0:
-            S, C, first = self._running, [[], []], self._n_folded
-        elif self.layer_N > 0:
-            S = self._layer_S(0)
-            C = self._layer_C(0)
-        else:
+        # the folded prefix (None when nothing is folded), then the stored layers
+        S, C = self._star_chain(self._running, [[], []], self._stored_layers(self._n_folded, self.layer_N))
+        self._zero_layer_S = S is None and not (self.has_in or self.has_out)           # reference stores 1-D zeros (rcwa.py:187-188)
+        if S is None:
             I = torch.eye(n, dtype=self._cdtype, device=self._device).expand(B, -1, -1).contiguous()
             Z = torch.zeros((B, n, n), dtype=self._cdtype, device=self._device)
             S = [I, Z, Z.clone(), I.clone()]
-            C = [[], []]
-            self._zero_layer_S = not (self.has_in or self.has_out)     # reference stores 1-D zeros (rcwa.py:187-188)
-        for i in range(first, self.layer_N):
-            S, C = self._star(S, self._layer_S(i), C, self._layer_C(i))
         sides = ([0] if self.has_in else []) + ([1] if self.has_out else [])           # rcwa.py:198-202, 204-208
         for j, side in enumerate(sides):
-            if (defer_last and j == len(sides) - 1 and not self.keep_coupling and not getattr(self, "_diff", False)
+            if (defer_last and j == len(sides) - 1 and not self.keep_coupling and not self._diff
                     and not self._is_bd(S) and not C[0] and not C[1]):
                 return S, C, side
             S, C = self._star(self._Sin, S, [[], []], C) if side == 0 else self._star(S, self._Sout, C, [[], []])
         return S, C, None
 
     def solve_global_smatrix(self):                                                     # rcwa.py:173-211
-        self._refuse_swept("solve_global_smatrix")
-        self._refuse_sector("solve_global_smatrix")
+        self._global_only("solve_global_smatrix")
         S, C, _ = self._cascade()
         if self._is_bd(S):                                                              # only homogeneous media: densify for the read-out
             S = [blk.dense().to(self._cdtype) for blk in S]
@@ -1125,10 +829,10 @@ class BatchedRCWA(FluxMixin, VolumeMixin):
         On a solver with a swept layer (add_layer(..., swept=True)) the result is [B, T, len(orders)], one row per thickness.
         With symmetry_sector=True only the mirror sectors that the requested columns touch are solved, cached per (layer, sector), and
         `self.S` / `self.C` are not set."""
-        if self.symmetry_sector:
-            return self._solve_sector(orders, direction, port, polarization, ref_order, power_norm, evanscent)
-        if self._swept is not None:
-            return self._solve_swept(orders, direction, port, polarization, ref_order, power_norm, evanscent)
+        solve = self._solve_sector if self.symmetry_sector else (self._solve_swept if self._swept is not None else self._solve_plain)
+        return solve(orders, direction, port, polarization, ref_order, power_norm, evanscent)
+
+    def _solve_plain(self, orders, direction, port, polarization, ref_order, power_norm, evanscent):
         orders, polarization, oi, ri, k = self._sparam_args(orders, direction, port, polarization, ref_order)
         S, C, side = self._cascade(defer_last=True)
         if side is None:
@@ -1138,190 +842,41 @@ class BatchedRCWA(FluxMixin, VolumeMixin):
             Sk = S[k]
             return self._sparam_values(lambda c: Sk[:, :, c], k, oi, ri, polarization, power_norm, evanscent)
         cols = self._sparam_columns(ri, polarization)
-        Sbd = self._Sin if side == 0 else self._Sout
-        bd = self._pack_bd(Sbd)
+        bd = self._pack_bd(self._Sin if side == 0 else self._Sout)
         out = self.engine.redheffer_halfspace_columns(side, bd, S, k, cols)             # [B, n, len(cols)]
         return self._sparam_values(lambda c: out[:, :, cols.index(c)], k, oi, ri, polarization, power_norm, evanscent)
 
-    # ---- a11 ---------------------------------------------------------------------------------------------
-    def _matching_indices(self, orders):                                                # rcwa.py:1115-1122
-        if self._general:         # position in the order list; the reference's clamping into the box applies to the rectangular path only
-            idx = []
-            for p, q in orders.reshape(-1, 2).tolist():
-                if (p, q) not in self._index:
-                    raise ValueError(f"harmonic ({p}, {q}) is not in this solver's order set")
-                idx.append(self._index[(p, q)])
-            return torch.as_tensor(idx, dtype=torch.int64, device=orders.device)
-        ox, oy = self.order
-        orders[orders[:, 0] < -ox, 0] = -ox
-        orders[orders[:, 0] > ox, 0] = ox
-        orders[orders[:, 1] < -oy, 1] = -oy
-        orders[orders[:, 1] > oy, 1] = oy
-        return len(self.order_y) * (orders[:, 0] + ox) + orders[:, 1] + oy
+    # ---- what a mode cannot serve: a swept solver has no single stack, a sector solver no global S-matrix and no coupling matrices.  Each mode
+    # states its refusal next to its code (_refuse_swept in swept.py, _refuse_sector in sector.py); S_parameters (readout.py) and
+    # solve_global_smatrix above call them as well
+    def _global_only(self, what):
+        self._refuse_swept(what)
+        self._refuse_sector(what)
 
-    def _kz_real(self, side, evan, abs_when_evanescent=False):
-        em = self.eps_in * self.mu_in if side == "in" else self.eps_out * self.mu_out
-        kzc = torch.sqrt(em[:, None] - self.Kx_norm_dn ** 2 - self.Ky_norm_dn ** 2)
-        ev = torch.abs(torch.real(kzc) / torch.imag(kzc)) < evan
-        repl = torch.abs(torch.real(kzc)) if abs_when_evanescent else torch.zeros_like(torch.real(kzc))
-        kz = torch.where(ev, repl, torch.real(kzc))
-        return torch.cat((kz, kz), dim=1)                                               # [B, n]
+    def power_flux(self, *a, **kw):
+        self._global_only("power_flux")
+        return super().power_flux(*a, **kw)
 
-    def _sparam_args(self, orders, direction, port, polarization, ref_order):
-        """Argument handling of S_parameters (rcwa.py:300-340): warnings and defaults for invalid names, the order -> index map (clamps `orders`
-        in place).  Returns (orders, polarization, oi, ri, k) with k the block of S the (direction, port) pair reads."""
-        dev = self._device
-        orders = torch.as_tensor(orders, dtype=torch.int64, device=dev).reshape([-1, 2])
-        if direction in _DIRS:
-            direction = _DIRS[direction]
-        else:
-            warnings.warn("Invalid propagation direction. Set as forward.", UserWarning)
-            direction = "forward"
-        if port in _PORTS:
-            port = _PORTS[port]
-        else:
-            warnings.warn("Invalid port. Set as tramsmission.", UserWarning)
-            port = "transmission"
-        if polarization not in ("xx", "yx", "xy", "yy", "pp", "sp", "ps", "ss"):
-            warnings.warn("Invalid polarization. Set as xx.", UserWarning)
-            polarization = "xx"
-        ref_order = torch.as_tensor(ref_order, dtype=torch.int64, device=dev).reshape([1, 2])
-        oi = self._matching_indices(orders)
-        ri = self._matching_indices(ref_order)
-        return orders, polarization, oi, ri, _SBLOCK[(direction, port)]
+    def incident_flux(self, *a, **kw):
+        self._global_only("incident_flux")
+        return super().incident_flux(*a, **kw)
 
-    def _sparam_columns(self, ri, polarization):
-        """Columns of the S block that _sparam_values reads: one in the xy basis, r0 and r0 + N in the ps basis."""
-        r0 = int(ri[0])
-        if polarization in ("xx", "yx", "xy", "yy"):
-            return [r0 + (self.order_N if polarization[1] == "y" else 0)]
-        return [r0, r0 + self.order_N]
+    def absorption(self, *a, **kw):
+        self._global_only("absorption")
+        return super().absorption(*a, **kw)
 
-    def S_parameters(self, orders, *, direction="forward", port="transmission", polarization="xx", ref_order=[0, 0],
-                     power_norm=True, evanscent=1e-3):                                  # rcwa.py:300-524
-        self._refuse_sector("S_parameters")
-        orders, polarization, oi, ri, k = self._sparam_args(orders, direction, port, polarization, ref_order)
-        Sk = self.S[k]
-        return self._sparam_values(lambda c: Sk[:, :, c], k, oi, ri, polarization, power_norm, evanscent)
+    def volume_integral(self, *a, **kw):
+        self._global_only("volume_integral")
+        return super().volume_integral(*a, **kw)
 
-    def _sparam_values(self, col, k, oi, ri, polarization, power_norm, evanscent):
-        """Read-out and normalisation of S_parameters from the columns of block k: col(c) -> [B, n], column c of S[k] (one of _sparam_columns)."""
-        N = self.order_N
-        num_side, den_side = _KZ_SIDES[k]
+    def absorption_by_region(self, *a, **kw):
+        self._global_only("absorption_by_region")
+        return super().absorption_by_region(*a, **kw)
 
-        if polarization in ("xx", "yx", "xy", "yy"):
-            if polarization[0] == "y":
-                oi = oi + N
-            if polarization[1] == "y":
-                ri = ri + N
-            val = col(int(ri[0]))[:, oi]                                                 # [B, M]
-            if power_norm:
-                kzn, kzd = self._kz_real(num_side, evanscent), self._kz_real(den_side, evanscent)
-                kxr = torch.cat((torch.real(self.Kx_norm_dn),) * 2, dim=1)
-                kyr = torch.cat((torch.real(self.Ky_norm_dn),) * 2, dim=1)
-                pn = kxr if polarization[0] == "x" else kyr                              # rcwa.py:368-375
-                pd = kxr if polarization[1] == "x" else kyr
-                norm = torch.sqrt((1 + (pn[:, oi] / kzn[:, oi]) ** 2) / (1 + (pd[:, ri] / kzd[:, ri]) ** 2))
-                norm = norm * torch.sqrt(kzn[:, oi] / kzd[:, ri])
-                val = val * norm
-            val = torch.where(torch.isinf(val), torch.zeros_like(val), val)
-            val = torch.where(torch.isnan(val), torch.zeros_like(val), val)
-            return val.to(self._dtype)
+    def source_planewave(self, *a, **kw):
+        self._refuse_sector("source_planewave")
+        return super().source_planewave(*a, **kw)
 
-        # ps basis                                                                         rcwa.py:410-521
-        osign, rsign = {0: (1, 1), 1: (-1, 1), 2: (1, -1), 3: (-1, -1)}[k]
-        em_in, em_out = self.eps_in * self.mu_in, self.eps_out * self.mu_out
-        ok2 = {0: em_out, 1: em_in, 2: em_out, 3: em_in}[k]
-        rk2 = {0: em_in, 1: em_in, 2: em_out, 3: em_out}[k]
-
-        def angles(idx, k2, sign):
-            kx_, ky_ = self.Kx_norm_dn[:, idx], self.Ky_norm_dn[:, idx]
-            kt = torch.sqrt(kx_ ** 2 + ky_ ** 2)
-            kzc = torch.sqrt(k2[:, None] - kx_ ** 2 - ky_ ** 2)
-            kzs = sign * torch.abs(torch.real(kzc))
-            ev = torch.abs(torch.real(kzc) / torch.imag(kzc)) < evanscent
-            return torch.atan2(torch.real(kt), kzs), torch.atan2(torch.real(ky_), torch.real(kx_)), ev
-
-        o_inc, o_azi, o_ev = angles(oi, ok2, osign)
-        r_inc, r_azi, r_ev = angles(ri, rk2, rsign)
-        r0 = int(ri[0])
-        c0, c1 = col(r0), col(r0 + N)
-        xx, xy = c0[:, oi], c1[:, oi]
-        yx, yy = c0[:, oi + N], c1[:, oi + N]
-        zero = torch.zeros_like(xx)
-        xx, xy, yx, yy = (torch.where(o_ev, zero, t) for t in (xx, xy, yx, yy))
-        co, so, ci = torch.cos(o_azi), torch.sin(o_azi), torch.cos(o_inc)
-        cr, sr, cri = torch.cos(r_azi), torch.sin(r_azi), torch.cos(r_inc)
-        if polarization == "pp":
-            val = co / ci * cri * cr * xx + so / ci * cri * cr * yx + co / ci * cri * sr * xy + so / ci * cri * sr * yy
-        elif polarization == "ps":
-            val = co / ci * (-1) * sr * xx + so / ci * (-1) * sr * yx + co / ci * cr * xy + so / ci * cr * yy
-        elif polarization == "sp":
-            val = -so * cri * cr * xx + co * cri * cr * yx + -so * cri * sr * xy + co * cri * sr * yy
-        else:
-            val = -so * (-1) * sr * xx + co * (-1) * sr * yx + -so * cr * xy + co * cr * yy
-        val = torch.where(torch.isinf(val), torch.zeros_like(val), val)
-        val = torch.where(torch.isnan(val), torch.zeros_like(val), val)
-        if power_norm:
-            kz_in = self._kz_real("in", evanscent)
-            kz_out = self._kz_real("out", evanscent, abs_when_evanescent=True)          # rcwa.py:495
-            kzn = kz_out if num_side == "out" else kz_in
-            kzd = kz_out if den_side == "out" else kz_in
-            val = val * torch.sqrt(kzn[:, oi] / kzd[:, ri])
-        val = torch.where(r_ev, torch.zeros_like(val), val)                             # rcwa.py:462-464 (per point)
-        return val.to(self._dtype)
-
-    def diffraction_angle(self, orders, *, layer="output", unit="radian"):               # rcwa.py:214-262
-        orders = torch.as_tensor(orders, dtype=torch.int64, device=self._device).reshape([-1, 2])
-        if layer in ("i", "in", "input"):
-            layer = "input"
-        elif layer in ("o", "out", "output"):
-            layer = "output"
-        else:
-            warnings.warn("Invalid layer. Set as output layer.", UserWarning)
-            layer = "output"
-        if unit in ("r", "rad", "radian"):
-            unit = "radian"
-        elif unit in ("d", "deg", "degree"):
-            unit = "degree"
-        else:
-            warnings.warn("Invalid unit. Set as radian.", UserWarning)
-            unit = "radian"
-        idx = self._matching_indices(orders)
-        eps = self.eps_in if layer == "input" else self.eps_out
-        mu = self.mu_in if layer == "input" else self.mu_out
-        kx, ky = self.Kx_norm_dn[:, idx], self.Ky_norm_dn[:, idx]
-        kt = torch.sqrt(kx ** 2 + ky ** 2)
-        kz = torch.sqrt((eps * mu)[:, None] - kx ** 2 - ky ** 2)
-        inc = torch.atan2(torch.real(kt), torch.real(kz))
-        azi = torch.atan2(torch.real(ky), torch.real(kx))
-        if unit == "degree":
-            inc, azi = (180. / PI_REF) * inc, (180. / PI_REF) * azi
-        return inc, azi
-
-
-def _refusing_swept(name):
-    """The mixin method `name`, refused on a solver with a swept layer or in sector mode."""
-    def method(self, *a, **kw):
-        self._refuse_swept(name)
-        self._refuse_sector(name)
-        return getattr(super(BatchedRCWA, self), name)(*a, **kw)
-    method.__name__ = name
-    return method
-
-
-for _name in ("power_flux", "incident_flux", "absorption", "volume_integral", "absorption_by_region"):
-    setattr(BatchedRCWA, _name, _refusing_swept(_name))
-
-
-def _refusing_sector(name):
-    """The mixin method `name`, refused in sector mode."""
-    def method(self, *a, **kw):
-        self._refuse_sector(name)
-        return getattr(super(BatchedRCWA, self), name)(*a, **kw)
-    method.__name__ = name
-    return method
-
-
-for _name in ("source_planewave", "source_fourier"):
-    setattr(BatchedRCWA, _name, _refusing_sector(_name))
+    def source_fourier(self, *a, **kw):
+        self._refuse_sector("source_fourier")
+        return super().source_fourier(*a, **kw)

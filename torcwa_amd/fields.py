@@ -62,7 +62,7 @@ class FieldMixin:
     def _mm(self, A, B):
         """[r,k] @ [k,c] on the HIP GEMM; through the autograd wrapper when the simulation was built on the differentiable
         path, so that field-based figures of merit can be back-propagated like in the reference (plain torch ops there)."""
-        if getattr(self._b, "_diff", False) and (A.requires_grad or B.requires_grad):
+        if self._b._diff and (A.requires_grad or B.requires_grad):
             from . import autograd_ops as ag
             return ag.GemmFn.apply(A[None].contiguous(), B[None].contiguous(), self._b.engine)[0]
         return self._b.engine.gemm(A[None].contiguous(), B[None].contiguous())[0]
@@ -159,7 +159,7 @@ class FieldMixin:
         if key not in cache:
             eng = self._b.engine
             E, M = self._b.eps_conv[layer_num], self._b.mu_conv[layer_num]
-            if getattr(self._b, "_diff", False) and (E.requires_grad or M.requires_grad):
+            if self._b._diff and (E.requires_grad or M.requires_grad):
                 from . import autograd_ops as ag
                 return ag.InverseFn.apply(E, eng)[0], ag.InverseFn.apply(M, eng)[0]      # graph-bound: not cached
             cache[key] = (eng.inverse(E)[0], eng.inverse(M)[0])

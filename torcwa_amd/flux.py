@@ -82,7 +82,7 @@ class FluxMixin:
             raise TrxError("power_flux / absorption need a source (call source_planewave() or source_fourier() first)")
 
     def _flux_diff(self, *tensors):
-        return getattr(self, "_diff", False) and torch.is_grad_enabled() and any(torch.is_tensor(t) and t.requires_grad for t in tensors)
+        return self._diff and self._requires_grad(*tensors)
 
     def _mv(self, A, x):
         """A [B,m,n] times x [B,n] -> [B,m]: trx_matvec, or GemmFn when a gradient is wanted."""
@@ -94,12 +94,6 @@ class FluxMixin:
     def _poynting(E, H, N):
         """Re sum_j (Ex_j conj(Hy_j) - Ey_j conj(Hx_j)) over dim 1 of [B, n, nz]."""
         return torch.real(E[:, :N] * torch.conj(H[:, N:]) - E[:, N:] * torch.conj(H[:, :N])).sum(dim=1)
-
-    def _bd_apply(self, bd, X):
-        """(2x2-block-diagonal operator) @ X for X [B, n, c]."""
-        N = self.order_N
-        d0, d1, d2, d3 = [t.to(self._cdtype)[:, :, None] for t in bd.d]
-        return torch.cat((d0 * X[:, :N] + d1 * X[:, N:], d2 * X[:, :N] + d3 * X[:, N:]), dim=1)
 
     def _halfspace_waves(self, side):
         """(E+ [B,n], E- [B,n], Vh, kz [B,n]) at z = 0 of the input (side -1) / output half-space: the amplitudes of fields.py (rcwa.py:639-696)."""
@@ -125,7 +119,7 @@ class FluxMixin:
         ph = torch.exp(1j * self.omega[:, None, None] * kz[:, :, None] * z[:, None, :].to(self._rdtype))      # [B, n, nz]
         Ep = Ep[:, :, None] * ph if parts != "-" else torch.zeros_like(ph)
         Em = Em[:, :, None] * torch.conj(ph) if parts != "+" else torch.zeros_like(ph)
-        return self._poynting(Ep + Em, self._bd_apply(Vh, Ep) - self._bd_apply(Vh, Em), self.order_N)
+        return self._poynting(Ep + Em, Vh.apply(Ep) - Vh.apply(Em), self.order_N)
 
     def _layer_flux(self, l, z):
         """Phi [B, nz] of internal layer l at offsets z [B, nz]."""
@@ -151,7 +145,7 @@ class FluxMixin:
         fwd = self.source_direction == "forward"
         Vh = (self._Vi if self.has_in else self._Vf) if fwd else (self._Vo if self.has_out else self._Vf)
         E = self._E_i[:, :, None]
-        H = self._bd_apply(Vh, E)
+        H = Vh.apply(E)
         return self._poynting(E, H if fwd else -H, self.order_N)[:, 0]
 
     def _z_arg(self, z_prop):

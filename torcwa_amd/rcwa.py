@@ -180,7 +180,7 @@ class rcwa(FieldMixin):
     @property
     def S(self):
         S = self._ul(self._b.S)
-        if getattr(self._b, "_zero_layer_S", False):        # rcwa.py:187-188 stores 1-D zeros in the no-layer case
+        if self._b._zero_layer_S:        # rcwa.py:187-188 stores 1-D zeros in the no-layer case
             n = 2 * self.order_N
             S[1] = torch.zeros(n, dtype=self._dtype, device=self._device)
             S[2] = torch.zeros(n, dtype=self._dtype, device=self._device)

@@ -13,7 +13,8 @@ import numpy as np
 import torch
 
 from .batched import NV_SIGMA_DEFAULT, BatchedRCWA, check_fourier_rule
-from .lattice import parse_order
+from .engine import default_engine
+from .memory import auto_chunk, auto_thickness_chunk  # noqa: F401  (the HBM model: re-exported, the benchmark and the tests take it from here)
 
 _DATA = os.path.join(os.path.dirname(os.path.abspath(__file__)), "data")
 
@@ -78,13 +79,13 @@ def rectangle_density(nx, ny, Lx, Ly, Wx, Wy, Cx, Cy, theta=0.0, edge_sharpness=
 
 
 def _solve_chunk(freq, layers, order, L, eps_in, eps_out, inc_ang, azi_ang, dtype, precision, engine, orders,
-                 polarization, direction, port, check_info, eig_route="auto", route_hint=None, fourier_rule="laurent", nv_sigma=NV_SIGMA_DEFAULT,
+                 polarization, direction, port, eig_route="auto", route_hint=None, fourier_rule="laurent", nv_sigma=NV_SIGMA_DEFAULT,
                  absorption=False, source=None, symmetry=None, symmetry_tol=1e-6, symmetry_sector=False):
     """layers: list of (thickness, eps[, mu]); thickness scalar or [b]; eps/mu scalar, [b] or [b,nx,ny].  absorption: the chunk keeps W, V and
     the coupling matrices (keep_coupling=True, no streaming cascade) and returns (S-parameters, BatchedRCWA.absorption())."""
     sim = BatchedRCWA(freq, order, L, dtype=dtype, precision=precision, engine=engine, keep_coupling=bool(absorption), fold_layers=not absorption,
                       eig_route=eig_route, route_hint=route_hint, fourier_rule=fourier_rule, nv_sigma=nv_sigma,
-                      symmetry=symmetry, symmetry_tol=symmetry_tol, **({"symmetry_sector": True} if symmetry_sector else {}))
+                      symmetry=symmetry, symmetry_tol=symmetry_tol, symmetry_sector=symmetry_sector)
     if eps_in is not None:
         sim.add_input_layer(eps=eps_in)
     if eps_out is not None:
@@ -104,78 +105,6 @@ def _solve_chunk(freq, layers, order, L, eps_in, eps_out, inc_ang, azi_ang, dtyp
     else:
         sim.source_planewave(**src)
     return sp, sim.absorption()
-
-
-# HBM footprint of one sweep point, in units of one n x n complex128 matrix (n = 2 (2 ox + 1)(2 oy + 1)): measured on MI355X with the caching
-# allocator -- single patterned layer, order [15,15], 128 points: 75.8 GB allocated / 111.8 GB reserved = 10.0 / 14.8 matrices per point; 4-layer stack
-# with the streaming cascade, order [21,21], 64 points: 228 / 247 GB = 16.3 / 17.6.  precision="native" halves the element.
-_POINT_MATRICES = {1: 15.0, 2: 18.0}          # layers == 1 / layers >= 2 (what the allocator RESERVES, which is what must fit)
-# fourier_rule="li": Ex and Ey (two N x N = n^2 / 4 matrices each) live next to E, E^-1 and the assembly workspace until A exists
-_LI_EXTRA = 0.5
-# fourier_rule="normal": Exx, Exy, Eyy (three N x N) next to E, E^-1 while A is built, and inside trx_convmat_nv the workspace ([1/eps], its
-# inverse's workspace and the three product matrices: five more N x N) -- 8 N^2 = 2 n^2
-_NV_EXTRA = 2.0
-_HEADROOM = 0.10                               # fraction of the device memory a sweep leaves free
-# Thickness sweep (add_layer(..., swept=True)), matrices per (point, thickness) that one trx_thickness_columns call holds, from its workspace
-# layout (include/trx.h): X rho X and K, 2 n x n; the amplitudes and the pivots are O(n m) and O(n) next to them.  They come on top of what stays
-# per point after the eigendecomposition -- W, V, rho_L, rho_R, A, B and the prepare workspace (7) and up to two dense sides (8) -- which is
-# below the eigensolver's peak that _POINT_MATRICES already covers.  Not measured on the allocator yet: auto_thickness_chunk() asks for what is free
-# at the time of the call, with the same headroom.
-_THICKNESS_MATRICES = 2.0
-
-
-# absorption=True (keep_coupling=True, no streaming cascade), matrices per point and layer on top of _POINT_MATRICES.  Derived from the code: every
-# layer keeps W, V, c+, c- (4), its S11, S21 (2) and, with the lean paths off, P, Q, M, M^-1 (4) = 10; the C lists hold one [2n, n] block per layer
-# in each direction (4 per layer), and a star product writes the new lists while the old ones are alive (4 per layer already folded) next to its
-# X / Y factors (4, once): 22 for one layer.  Measured on MI355X (profiles/flux_timing.txt: single patterned layer, order [15,15], 120 points):
-# 188.1 GB allocated / 210.9 GB reserved = 26.5 / 29.7 matrices per point in all, against 10.0 / 14.2 for the plain sweep -- the derived count was
-# too high (not all of its terms are alive at once).  What must fit is what the allocator reserves: 29.7 - 15.0 (_POINT_MATRICES) = 14.7 -> 15.
-# Only the one-layer case is measured; the count is applied per layer because every term of the derivation grows with the number of layers.
-_ABS_EXTRA_PER_LAYER = 15.0
-
-
-def auto_chunk(B, order, n_layers, precision, device, dtype=torch.complex64, streams=1, fourier_rule="laurent", absorption=False):
-    """Largest number of points solved in lock-step that fits the free HBM of `device` with _HEADROOM to spare (a multiple of 8 when it
-    is cut: the mixed-precision eigensolver and its iteration groups want batches of at least 8).  Raises with the numbers when not even
-    one point fits -- instead of an allocator error in the middle of a solve."""
-    if device.type != "cuda":
-        return B
-    kind, box, mn = parse_order(order)          # [ox, oy] or an [N, 2] order list (oblique lattices, circular truncation): n = 2N
-    n = 2 * (2 * box[0] + 1) * (2 * box[1] + 1) if kind == "rect" else 2 * len(mn)
-    # element size of the COMPUTE dtype: complex128 unless a complex64 problem is solved natively (BatchedRCWA: precision="native" only
-    # halves the element of complex64 problems); `streams` chunks are resident at once when the sweep is dealt to several streams
-    elem = 8 if (precision == "native" and dtype == torch.complex64) else 16
-    mats = _POINT_MATRICES[1 if n_layers <= 1 else 2] + {"li": _LI_EXTRA, "normal": _NV_EXTRA}.get(fourier_rule, 0.0)
-    if absorption:
-        mats += _ABS_EXTRA_PER_LAYER * max(1, int(n_layers))
-    per_point = mats * n * n * elem * max(1, int(streams))
-    free, total = torch.cuda.mem_get_info(device)
-    free += torch.cuda.memory_reserved(device) - torch.cuda.memory_allocated(device)      # the caching allocator's idle blocks are ours to reuse
-    budget = free - _HEADROOM * total
-    fit = int(budget // per_point)
-    if fit < 1:
-        raise RuntimeError("torcwa_amd sweep: one sweep point at order %s needs about %.1f GB of HBM (%d x %d complex matrices x %.0f), but only "
-                           "%.1f GB are free on %s (%.1f GB total, %.0f %% kept as headroom); free memory or lower the order"
-                           % (list(box) if kind == "rect" else "of %d harmonics" % len(mn), per_point / 1e9, n, n, mats, free / 1e9, device, total / 1e9, 100 * _HEADROOM))
-    if fit >= B:
-        return B
-    return fit if fit < 8 else fit - fit % 8
-
-
-def auto_thickness_chunk(B, T, n, m, cdtype, device):
-    """Thicknesses per trx_thickness_columns call that fit the free HBM of `device` next to B resident points (_THICKNESS_MATRICES), with
-    _HEADROOM to spare; T when everything fits.  Raises with the numbers when not even one thickness fits."""
-    if device.type != "cuda":
-        return T
-    elem = 16 if cdtype == torch.complex128 else 8
-    per = B * ((_THICKNESS_MATRICES * n * n + 5 * n * m) * elem + 4 * (n + 1))
-    free, total = torch.cuda.mem_get_info(device)
-    free += torch.cuda.memory_reserved(device) - torch.cuda.memory_allocated(device)
-    fit = int((free - _HEADROOM * total) // per)
-    if fit < 1:
-        raise RuntimeError("torcwa_amd thickness sweep: one thickness of %d points needs about %.1f GB of HBM (%d x %d complex matrices x %.0f per "
-                           "point), but only %.1f GB are free on %s; lower the chunk of points" % (B, per / 1e9, n, n, _THICKNESS_MATRICES, free / 1e9, device))
-    return min(int(T), fit)
 
 
 def _slice(v, lo, hi, B):
@@ -228,46 +157,54 @@ def solve_stack_sweep(freq, layers, order, L, *, eps_in=None, eps_out=None, inc_
     input -- and the call returns
     (S-parameters, absorption dict) with the dict's tensors ("layers" [B, n_layers], "R", "T", "A" [B]) concatenated over the chunks.  With the
     default absorption=False the code path, the return value and the memory model are unchanged."""
-    from .engine import default_engine
     check_fourier_rule(fourier_rule)
     if symmetry_sector and absorption:
         raise ValueError("symmetry_sector=True is not available with absorption=True: a sector solve keeps no coupling matrices")
     if symmetry_sector and symmetry is None:
         raise ValueError('symmetry_sector=True needs symmetry="x" | "y" | "xy"')
     B = freq.shape[0]
-    eng = engine if engine is not None else default_engine()
-    old_check, eng.check_info = eng.check_info, check_info         # restored below: the engine may be shared with other solvers
-    # chunk=None: as many points in lock-step as the free HBM holds (the reference's per-point loop cannot run out of memory; neither must this)
-    chunk = (auto_chunk(B, order, len(layers), precision, freq.device, dtype=dtype, streams=streams, fourier_rule=fourier_rule,
-                        **({"absorption": True} if absorption else {})) if not chunk
-             else int(chunk))
-    if streams > 1 and chunk >= B:
-        chunk = -(-B // streams)
-    spans = [(lo, min(B, lo + chunk)) for lo in range(0, B, chunk)]
-    outs = [None] * len(spans)
-    route_hint = {}                     # shared by the chunks of this call only
     n_src, src_per_point = _source_amplitudes(source, B) if absorption else (1, False)
 
-    def run(i):
-        lo, hi = spans[i]
+    def solve(lo, hi, route_hint):
         lays = [tuple(_slice(v, lo, hi, B) for v in lay) for lay in layers]
         src = source
         if src_per_point:
             src = dict(source, amplitude=torch.as_tensor(source["amplitude"]).reshape(B, n_src, 2)[lo:hi])
-        outs[i] = _solve_chunk(freq[lo:hi], lays, order, L, _slice(eps_in, lo, hi, B), _slice(eps_out, lo, hi, B), _slice(inc_ang, lo, hi, B),
-                               _slice(azi_ang, lo, hi, B), dtype, precision, engine, orders, polarization, direction, port, check_info,
-                               eig_route=eig_route, route_hint=route_hint, fourier_rule=fourier_rule, nv_sigma=nv_sigma,
-                               **({"absorption": True, "source": src} if absorption else {}),
-                               symmetry=symmetry, symmetry_tol=symmetry_tol, **({"symmetry_sector": True} if symmetry_sector else {}))
+        return _solve_chunk(freq[lo:hi], lays, order, L, _slice(eps_in, lo, hi, B), _slice(eps_out, lo, hi, B), _slice(inc_ang, lo, hi, B),
+                            _slice(azi_ang, lo, hi, B), dtype, precision, engine, orders, polarization, direction, port,
+                            eig_route=eig_route, route_hint=route_hint, fourier_rule=fourier_rule, nv_sigma=nv_sigma, absorption=absorption,
+                            source=src if absorption else None, symmetry=symmetry, symmetry_tol=symmetry_tol, symmetry_sector=symmetry_sector)
 
-    dev = freq.device
-    try:
-        _run_spans(run, spans, streams, dev)
-    finally:
-        eng.check_info = old_check
+    # chunk=None: as many points in lock-step as the free HBM holds (the reference's per-point loop cannot run out of memory; neither must this)
+    outs = _solve_chunks(solve, B, freq.device, engine, check_info, streams, chunk or (lambda: auto_chunk(
+        B, order, len(layers), precision, freq.device, dtype=dtype, streams=streams, fourier_rule=fourier_rule, absorption=absorption)))
     if absorption:
         return (torch.cat([o[0] for o in outs], dim=0), {k: torch.cat([o[1][k] for o in outs], dim=0) for k in outs[0][1]})
     return torch.cat(outs, dim=0)
+
+
+def _solve_chunks(solve, B, dev, engine, check_info, streams, chunk):
+    """What the sweep drivers share: the B points are cut into chunks of `chunk` points (an int, or a callable that chooses it once the engine
+    is set), the chunks are dealt to `streams` streams, and solve(lo, hi, route_hint) -> the result of points lo .. hi - 1 is called for each;
+    route_hint is the dict the chunks of this one call share (BatchedRCWA._eig_call).  Returns the results in sweep order.  The engine's
+    check_info is set for the call and restored: the engine may be shared with other solvers."""
+    eng = engine if engine is not None else default_engine()
+    old_check, eng.check_info = eng.check_info, check_info
+    try:
+        chunk = int(chunk() if callable(chunk) else chunk)
+        if streams > 1 and chunk >= B:
+            chunk = -(-B // streams)
+        spans = [(lo, min(B, lo + chunk)) for lo in range(0, B, chunk)]
+        outs = [None] * len(spans)
+        route_hint = {}
+
+        def run(i):
+            outs[i] = solve(*spans[i], route_hint)
+
+        _run_spans(run, spans, streams, dev)
+    finally:
+        eng.check_info = old_check
+    return outs
 
 
 def _run_spans(run, spans, streams, dev):
@@ -324,7 +261,6 @@ def solve_thickness_sweep(freq, layers, order, L, *, layer=0, thicknesses, eps_i
     layers as in solve_stack_sweep; the thickness entry of layers[layer] is ignored and may be None.  thicknesses: [T] (shared by the points)
     or [B, T].  Keywords as solve_stack_sweep, without absorption / source (a swept solve keeps no coupling matrices).  chunk: points solved in
     lock-step (default: auto_chunk); thickness_chunk: thicknesses per library call (default: what the free HBM holds, `auto_thickness_chunk`)."""
-    from .engine import default_engine
     check_fourier_rule(fourier_rule)
     B = freq.shape[0]
     layer = int(layer)
@@ -338,17 +274,8 @@ def solve_thickness_sweep(freq, layers, order, L, *, layer=0, thicknesses, eps_i
         per_point = True
     else:
         raise ValueError(f"thicknesses must be [T] or [{B}, T], got {list(d.shape)}")
-    eng = engine if engine is not None else default_engine()
-    old_check, eng.check_info = eng.check_info, check_info
-    chunk = auto_chunk(B, order, len(layers), precision, freq.device, dtype=dtype, streams=streams, fourier_rule=fourier_rule) if not chunk else int(chunk)
-    if streams > 1 and chunk >= B:
-        chunk = -(-B // streams)
-    spans = [(lo, min(B, lo + chunk)) for lo in range(0, B, chunk)]
-    outs = [None] * len(spans)
-    route_hint = {}
 
-    def run(i):
-        lo, hi = spans[i]
+    def solve(lo, hi, route_hint):
         sim = BatchedRCWA(freq[lo:hi], order, L, dtype=dtype, precision=precision, engine=engine, keep_coupling=False, fold_layers=True,
                           eig_route=eig_route, route_hint=route_hint, fourier_rule=fourier_rule, nv_sigma=nv_sigma, symmetry=symmetry,
                           symmetry_tol=symmetry_tol)
@@ -364,10 +291,7 @@ def solve_thickness_sweep(freq, layers, order, L, *, layer=0, thicknesses, eps_i
                 sim.add_layer(d[lo:hi] if per_point else d, *lay[1:], swept=True)
             else:
                 sim.add_layer(*lay)
-        outs[i] = sim.solve_S_parameters([list(o) for o in orders], direction=direction, port=port, polarization=polarization)
+        return sim.solve_S_parameters([list(o) for o in orders], direction=direction, port=port, polarization=polarization)
 
-    try:
-        _run_spans(run, spans, streams, freq.device)
-    finally:
-        eng.check_info = old_check
-    return torch.cat(outs, dim=0)
+    return torch.cat(_solve_chunks(solve, B, freq.device, engine, check_info, streams, chunk or (lambda: auto_chunk(
+        B, order, len(layers), precision, freq.device, dtype=dtype, streams=streams, fourier_rule=fourier_rule))), dim=0)
