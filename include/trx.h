@@ -408,7 +408,22 @@ int trx_modal_overlap(int dtype, const void* M, const void* cplus, const void* c
  * layout of one block of trx_redheffer_halfspace's bd): the dense out [batch,n_kl,n_kr], zeros included.  Serves Vf^-1 (pair k, k'), the blocks
  * of Sin / Sout and of a homogeneous layer's S-matrix (pair k, k).  Traffic model: the 4 N diagonal entries read, n_kl n_kr written.
  * N <= 16384.
- * All six: stream-ordered, no host synchronisation, deterministic, no atomics; complex64 and complex128; n^2 < 2^31, batch <= 65535,
+ * Adjoints of the sector folds, in PyTorch's complex convention; they make a sector solve differentiable.  Both read the ROW plan ridx / rwt of
+ * trx_sym_fold_backward: a gather with one writer per element, no zero fill, no workspace, no atomics; indices are clamped into their block.
+ * trx_sym_fold_pairs_backward: the adjoint of npairs trx_sym_fold_pair calls on the same M, in one pass:
+ *   gM[r,c] = sum_p rwt[r,kl_p] G_p[ridx[r,kl_p] - off[kl_p], ridx[c,kr_p] - off[kr_p]] conj(rwt[c,kr_p])      (gM = sum_p T_kl_p G_p T_kr_p^H)
+ * G: HOST array of npairs device pointers, G_p [batch,n_kl_p,n_kr_p]; kl, kr: HOST arrays of npairs block indices; 0 <= npairs <= 16.  The table
+ * travels to the kernel by value: no device-side pointer array.  A null G_p is a pair whose output took no gradient: it is skipped (its kl, kr are
+ * still checked).  Every element of gM [batch,n,n] is written: 0 where no pair reaches, all zeros when every pointer is null or npairs = 0.  A pair
+ * may occur more than once.  A malformed off fills gM with NaN.  A layer folds P on the pairs (k, k') and Q on (k', k) of every block k: one call
+ * per matrix writes n^2 once, where nblk calls would each write n^2 and leave nblk - 1 full-size additions to the caller.  Traffic model (elements
+ * per matrix): n^2 written, at most one element of G_p read per element and pair whose two weights are non-zero: at most (1 + npairs) n^2, and
+ * (1 + 1 / nblk) n^2 distinct (the pairs (k, k') of all k hold n^2 / nblk elements; an orbit re-reads its element in the same rows).
+ * trx_sym_fold_pair_bd_backward: the adjoint of ONE trx_sym_fold_pair_bd: the four diagonals gbd [4][batch][N] of T_kl G T_kr^H,
+ *   gbd[2p+q][b][m] = rwt[pN+m,kl] G[b][ridx[pN+m,kl] - off[kl], ridx[qN+m,kr] - off[kr]] conj(rwt[qN+m,kr]),   p, q in {0, 1},
+ * from G [batch,n_kl,n_kr].  All 4 batch N entries are written, 0 where a weight is 0; a malformed off fills them with NaN.  O(N) work: at most
+ * 4 N elements of G read and 4 N written per matrix; the caller sums over pairs.  N <= 16384.
+ * All eight: stream-ordered, no host synchronisation, deterministic, no atomics; complex64 and complex128; n^2 < 2^31, batch <= 65535,
  * 1 <= nblk <= 4, else TRX_ERR_ARG (also for kl or kr outside [0, nblk)); batch = 0 returns TRX_OK without touching any buffer.  Element
  * alignment suffices for every buffer but ws. */
 size_t trx_sym_fold_ws_bytes(int dtype, int n, int batch);
@@ -424,6 +439,10 @@ int trx_sym_fold_pair(int dtype, const void* M, int n, int batch, const int* idx
                       void* out, void* stream);
 int trx_sym_fold_pair_bd(int dtype, const void* bd, int N, int batch, const int* idx, const void* wt, const int* off, int nblk, int kl, int kr,
                          void* out, void* stream);
+int trx_sym_fold_pairs_backward(int dtype, const void* const* G, const int* kl, const int* kr, int npairs, int n, int batch, const int* ridx,
+                                const void* rwt, const int* off, int nblk, void* gM, void* stream);
+int trx_sym_fold_pair_bd_backward(int dtype, const void* G, int N, int batch, const int* ridx, const void* rwt, const int* off, int nblk, int kl,
+                                  int kr, void* gbd, void* stream);
 
 /* ---- thickness sweeps that reuse a layer's modes (no reference counterpart; what modal solvers offer as a layer-thickness scan) ----------------
  * The modes W, kz, V of a layer do not depend on its thickness d, only the diagonal phase X = exp(i omega kz d) does.  With F = Vf^-1 V (the
@@ -479,7 +498,8 @@ int trx_thickness_columns(int dtype, const void* rhoL, const void* rhoR, const v
  * 3 QR off-window update; 4 QR window chase; 5 Hessenberg gemv; 6 Hessenberg reflector column; 7 LU panel; 8 - 15 see trx_prof_tag_name;
  * 16 trx_sym_fold (both passes); 17 trx_sym_unfold (zero fill and scatter); 18 trx_thickness_prepare (whole call); 19 - 21 the stages of
  * trx_thickness_columns, one event pair per call each: 19 K assembly and its GEMMs, 20 LU of K and the column solve, 21 amplitudes and read-out;
- * 22 trx_sym_fold_backward; 23 trx_sym_unfold_backward; 24 trx_sym_fold_pair; 25 trx_sym_fold_pair_bd. */
+ * 22 trx_sym_fold_backward; 23 trx_sym_unfold_backward; 24 trx_sym_fold_pair; 25 trx_sym_fold_pair_bd; 26 trx_sym_fold_pairs_backward;
+ * 27 trx_sym_fold_pair_bd_backward. */
 int trx_prof_enable(int on);
 int trx_prof_reset(void);
 int trx_prof_get(int tag, double* out);

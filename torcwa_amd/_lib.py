@@ -82,7 +82,10 @@ _SIGS = {
     "trx_sym_unfold_backward": (c_int, [c_int, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p]),
     "trx_sym_fold_pair": (c_int, [c_int, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
     "trx_sym_fold_pair_bd": (c_int, [c_int, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
-    "trx_thickness_prepare_ws_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "trx_sym_fold_pairs_backward": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p,
+                                            c_void_p]),
+    "trx_sym_fold_pair_bd_backward": (c_int, [c_int, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
+    "trx_thickness_prepare_ws_bytes":(c_size_t, [c_int, c_int, c_int]),
     "trx_thickness_prepare": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_int, c_int,
                                       c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "trx_thickness_columns_ws_bytes": (c_size_t, [c_int, c_int, c_int, c_int, c_int]),

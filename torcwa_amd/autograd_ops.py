@@ -228,3 +228,35 @@ class SymUnfoldFn(torch.autograd.Function):
     def backward(ctx, glam, gW):
         gWk, glamk = ctx.engine.sym_unfold_backward(gW, glam, ctx.plan)
         return (None, None, *gWk, *glamk)
+
+
+class SymFoldPairsFn(torch.autograd.Function):
+    """One [B, n_kl, n_kr] tensor per (kl, kr) of `pairs`: T_kl^H M T_kr (engine.sym_fold_pair per pair).  A fold is linear: nothing is saved,
+    and the full-size M is not kept alive.  backward: ONE trx_sym_fold_pairs_backward, gM = sum_p T_kl_p G_p T_kr_p^H; an output that took no
+    gradient travels as a null pointer."""
+
+    @staticmethod
+    def forward(ctx, M, plan, engine, pairs):
+        ctx.engine, ctx.plan, ctx.pairs = engine, plan, [(int(kl), int(kr)) for kl, kr in pairs]
+        ctx.meta = (M.shape[0], M.dtype)
+        ctx.set_materialize_grads(False)
+        return tuple(engine.sym_fold_pair(M, plan, kl, kr) for kl, kr in ctx.pairs)
+
+    @staticmethod
+    def backward(ctx, *grads):
+        B, dt = ctx.meta
+        return ctx.engine.sym_fold_pairs_backward(list(grads), ctx.plan, ctx.pairs, B=B, dtype=dt), None, None, None
+
+
+class SymFoldPairBdFn(torch.autograd.Function):
+    """[B, n_kl, n_kr] = T_kl^H M T_kr of a 2x2-block-diagonal M given as its four diagonals bd [4,B,N] (engine.sym_fold_pair_bd); nothing is
+    saved.  backward: the four diagonals of T_kl G T_kr^H (trx_sym_fold_pair_bd_backward)."""
+
+    @staticmethod
+    def forward(ctx, bd, plan, engine, kl, kr):
+        ctx.engine, ctx.plan, ctx.pair = engine, plan, (int(kl), int(kr))
+        return engine.sym_fold_pair_bd(bd, plan, kl, kr)
+
+    @staticmethod
+    def backward(ctx, G):
+        return ctx.engine.sym_fold_pair_bd_backward(G, ctx.plan, *ctx.pair), None, None, None, None

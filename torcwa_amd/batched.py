@@ -43,7 +43,7 @@ Medium = namedtuple("Medium", "E Einv M Minv eps_s mu_s exx exy eyy mx my")
 #   handed to add_layer, by reference (a grid) or as the per-point scalar [B] (absorption_by_region); eps_conv_x / _y (fourier_rule="li" with
 #   keep_coupling): Li's Ex, Ey; eps_conv_xx / _xy / _yy (fourier_rule="normal" with keep_coupling): the tensor Exx, Exy (= Eyx), Eyy;
 #   symmetry_residual: resid [B] of trx_sym_fold (the discarded part of T^H A T relative to max |A|); _sector_layers (symmetry_sector):
-#   dict(P=[P_k], Q=[Q_k]) of a patterned layer
+#   dict(P=[P_k], Q=[Q_k]) of a patterned layer, with diff=True when they came through SymFoldPairsFn (sector_grad)
 _CONV_FIELDS = ("eps_conv", "eps_conv_x", "eps_conv_y", "eps_conv_xx", "eps_conv_xy", "eps_conv_yy")     # what a folded layer drops
 _LAYER_FIELDS = ("thickness", "mu_conv", "eps_grid", "mu_grid", "P", "Q", "kz_norm", "E_eigvec", "H_eigvec", "Cplus", "Cminus",
                  "layer_S11", "layer_S21", "symmetry_residual", "_sector_layers") + _CONV_FIELDS
@@ -71,7 +71,7 @@ class BatchedRCWA(FluxMixin, VolumeMixin, ReadoutMixin, SectorMixin, SweptMixin)
     def __init__(self, freq, order, L, *, batch=None, dtype=torch.complex64, device=None, stable_eig_grad=True,
                  avoid_Pinv_instability=False, max_Pinv_instability=0.005, precision="high", engine=None,
                  keep_coupling=True, fold_layers=False, eig_route="auto", route_hint=None, fourier_rule="laurent", nv_sigma=NV_SIGMA_DEFAULT,
-                 symmetry=None, symmetry_tol=1e-6, symmetry_grad=False, symmetry_sector=False):
+                 symmetry=None, symmetry_tol=1e-6, symmetry_grad=False, symmetry_sector=False, sector_grad=False):
         check_fourier_rule(fourier_rule)
         # symmetry (extension): None | "x" | "y" | "xy" -- the caller states that every patterned layer is invariant under x -> -x (y -> -y) about
         # a plane and that kx0 = 0 (ky0 = 0) at every sweep point.  A = P Q of such a layer is then folded into 2 / 4 independent eigenproblems
@@ -92,6 +92,12 @@ class BatchedRCWA(FluxMixin, VolumeMixin, ReadoutMixin, SectorMixin, SweptMixin)
         # symmetry_sector=True (opt-in; needs symmetry=): only the mirror sectors a read-out touches are solved (sector.py).  False: the
         # paths below.
         self.symmetry_sector = bool(symmetry_sector)
+        # sector_grad=True (opt-in; needs symmetry_sector=True): a layer whose tensors require grad goes through the differentiable twin of the
+        # sector path (SymFoldPairsFn, GemmFn, Eig, InverseFn on the sector's block).  P and Q themselves are folded, so the RAW per-pixel
+        # gradient is the mirror average of the unfolded path's gradient (sector.py).  symmetry_grad is then accepted and not read.
+        self.sector_grad = bool(sector_grad)
+        if self.sector_grad and not self.symmetry_sector:
+            raise ValueError("sector_grad=True needs symmetry_sector=True")
         if self.symmetry_sector:
             self._check_sector(keep_coupling, avoid_Pinv_instability)
         self._sector_centres = None      # (cx, nx, cy, ny) of the first patterned layer: the one plan of the whole stack
@@ -625,8 +631,9 @@ class BatchedRCWA(FluxMixin, VolumeMixin, ReadoutMixin, SectorMixin, SweptMixin)
         return S11, S21, V, cp, cm, W
 
     def _RS_prod_diff(self, Sm, Sn, Cm, Cn):
-        """Star product (rcwa.py:1283-1306) from differentiable primitives (one factorisation, push-through identity)."""
-        eng, n = self.engine, self.n
+        """Star product (rcwa.py:1283-1306) from differentiable primitives (one factorisation, push-through identity).  The size comes from
+        the operand: the blocks of a sector (sector.py) are about n / 4."""
+        eng, n = self.engine, Sm[0].shape[-1]
         I = torch.eye(n, dtype=self._cdtype, device=self._device)
         mm = lambda a, b: ag.GemmFn.apply(a.contiguous(), b.contiguous(), eng)
         K = I - mm(Sm[2], Sn[1])
@@ -828,7 +835,7 @@ class BatchedRCWA(FluxMixin, VolumeMixin, ReadoutMixin, SectorMixin, SweptMixin)
         half-space, only homogeneous layers -- runs solve_global_smatrix() and reads out of self.S as S_parameters does.
         On a solver with a swept layer (add_layer(..., swept=True)) the result is [B, T, len(orders)], one row per thickness.
         With symmetry_sector=True only the mirror sectors that the requested columns touch are solved, cached per (layer, sector), and
-        `self.S` / `self.C` are not set."""
+        `self.S` / `self.C` are not set; with sector_grad=True the result carries the graph of those sectors (read-outs of one sector share it)."""
         solve = self._solve_sector if self.symmetry_sector else (self._solve_swept if self._swept is not None else self._solve_plain)
         return solve(orders, direction, port, polarization, ref_order, power_norm, evanscent)
 

@@ -17,7 +17,9 @@ enum ProfTag { PROF_GEMM_NN = 0, PROF_GEMM_OTHER = 1, PROF_QR_PREPARE = 2, PROF_
                // adjoints of the folding (symfold.hip): trx_sym_fold_backward, trx_sym_unfold_backward
                PROF_SYM_FOLD_BWD = 22, PROF_SYM_UNFOLD_BWD = 23,
                // sector folds (symfold.hip): trx_sym_fold_pair, trx_sym_fold_pair_bd
-               PROF_SYM_FOLD_PAIR = 24, PROF_SYM_FOLD_PAIR_BD = 25, PROF_NTAGS = 26 };
+               PROF_SYM_FOLD_PAIR = 24, PROF_SYM_FOLD_PAIR_BD = 25,
+               // adjoints of the sector folds (symfold.hip): trx_sym_fold_pairs_backward, trx_sym_fold_pair_bd_backward
+               PROF_SYM_FOLD_PAIRS_BWD = 26, PROF_SYM_FOLD_PAIR_BD_BWD = 27, PROF_NTAGS = 28 };
 // (PROF_GEMM_*_F32: the fp32 GEMMs -- first stage of the mixed-precision eigensolver, precision="native" -- are counted apart from the fp64 ones:
 // other peak, other roofline)
 

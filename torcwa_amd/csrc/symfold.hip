@@ -37,6 +37,18 @@
 //   ceil(n / SF_ROWS) row groups and the groups beyond n_kl leave at once.  No workspace, no atomics: every element has one writer.
 // Traffic model per matrix: at most 16 n_kl n_kr elements read and n_kl n_kr written, 17 (n / nblk)^2: about n^2 per pair for two mirrors.  _bd
 //   reads the 4 N diagonal entries (the 16 candidates of an element are index tests, not loads) and writes n_kl n_kr.
+//
+// Adjoints of the sector folds (trx_sym_fold_pairs_backward, trx_sym_fold_pair_bd_backward), from the ROW plan like fold backward.
+//   pairs backward   gM = sum_p T_kl_p G_p T_kr_p^H for up to SF_MAXPAIRS pairs in ONE pass (a layer folds P on the pairs (k, k') and Q on (k', k)
+//                    of every block): gM[r, c] = sum_p rwt[r][kl_p] G_p[ridx[r][kl_p] - off[kl_p], ridx[c][kr_p] - off[kr_p]] conj(rwt[c][kr_p]).
+//                    The lane mapping of fold backward: the lanes of a wave walk c, the writes are coalesced and the gathers of one row stay inside
+//                    one row of each G_p.  The pair table (pointers, kl, kr) is a kernel argument passed by value; a null pointer is a pair without
+//                    a gradient.  One writer per element, every element written: no zero fill, workspace or atomics.
+//   pair_bd backward the four diagonals of T_kl G T_kr^H: one thread per m, the elements (p N + m, q N + m), p, q in {0, 1}.
+// Traffic model per matrix: pairs backward writes n^2 and reads one element of G_p per element and pair whose two weights are non-zero: counted
+// as (1 + npairs) n^2 at most -- for the pairs (k, k') of all k every (r, c) meets up to nblk pairs, but the distinct elements are
+// sum_k n_k n_k' ~ n^2 / nblk and the re-reads of an orbit fall in the same rows; 2 n plan rows per SF_ROWS rows.  HBM-bound.  pair_bd backward
+// reads at most 4 N elements of G (scattered: one per diagonal entry) and writes 4 N.
 #include "common.hpp"
 #include "prof.hpp"
 
@@ -47,6 +59,7 @@ namespace {
 constexpr int SF_THREADS = 256;
 constexpr int SF_ROWS = 8;        // rows of the output per workgroup
 constexpr int SF_MAXBLK = 4;
+constexpr int SF_MAXPAIRS = 16;   // pairs of one trx_sym_fold_pairs_backward call: all nblk^2 of two mirrors
 
 // Block offsets and the packing of the per-block arrays: blocks of equal size form one group, groups in the order of their first block;
 // a group of g blocks of size s is one contiguous [g, batch, u] region, u = s * s (matrices) or s (eigenvalues).
@@ -404,6 +417,139 @@ __global__ __launch_bounds__(SF_THREADS) void sym_fold_pair_kernel(const cx<T>* 
     }
 }
 
+// The pair table of trx_sym_fold_pairs_backward: a kernel argument, passed by value.  g[p] null: a pair whose output took no gradient.
+struct PairTable {
+    const void* g[SF_MAXPAIRS];
+    signed char kl[SF_MAXPAIRS], kr[SF_MAXPAIRS];
+    int np;
+};
+
+// Offset and size of every block from off as given (sizes held inside [0, n], 0 for k >= nblk), and pair_extent's verdict on off.
+struct BlockExtents {
+    int ok, o[SF_MAXBLK], s[SF_MAXBLK];
+};
+
+__device__ __forceinline__ BlockExtents block_extents(const int* __restrict__ off, int nblk, int n) {
+    BlockExtents E;
+    E.ok = off[0] == 0 && off[nblk] == n;
+#pragma unroll
+    for (int k = 0; k < SF_MAXBLK; ++k) {
+        E.o[k] = E.s[k] = 0;
+        if (k >= nblk) continue;
+        E.ok = E.ok && off[k + 1] >= off[k];
+        const long d = (long)off[k + 1] - off[k];
+        E.o[k] = off[k];
+        E.s[k] = d < 0 ? 0 : (d > n ? n : (int)d);
+    }
+    return E;
+}
+
+// a[k] for a wave-uniform k, by selects: the array stays in registers
+template <class V> __device__ __forceinline__ V pick(const V (&a)[SF_MAXBLK], int k) {
+    V v = a[0];
+#pragma unroll
+    for (int e = 1; e < SF_MAXBLK; ++e) v = k == e ? a[e] : v;
+    return v;
+}
+
+// gM = sum_p T_kl_p G_p T_kr_p^H from the row plan.  grid (ceil(n / SF_ROWS), batch); a malformed off fills gM with NaN.  The table reaches LDS
+// through thread 0 with static indices (a run-time index into a by-value argument would go through scratch); then one thread per (row, pair)
+// stages what the row contributes: T's entry and the row of G_p[b] it reads, null where the pair does not reach the row.
+template <class T>
+__global__ __launch_bounds__(SF_THREADS) void sym_fold_pairs_bwd_kernel(const PairTable P, const int* __restrict__ ridx, const cx<T>* __restrict__ rwt,
+                                                                        const int* __restrict__ off, int nblk, int n, int batch,
+                                                                        cx<T>* __restrict__ gM) {
+    __shared__ const void* sg[SF_MAXPAIRS];
+    __shared__ int skl[SF_MAXPAIRS], skr[SF_MAXPAIRS];
+    __shared__ const void* srow[SF_ROWS * SF_MAXPAIRS];
+    __shared__ T swx[SF_ROWS * SF_MAXPAIRS], swy[SF_ROWS * SF_MAXPAIRS];
+    const int tid = threadIdx.x, b = blockIdx.y, r0 = blockIdx.x * SF_ROWS;
+    const BlockExtents E = block_extents(off, nblk, n);
+    cx<T>* Mb = gM + (long)b * n * n;
+    const int rows = n - r0 < SF_ROWS ? n - r0 : SF_ROWS;
+    if (!E.ok) {                                                                        // the whole workgroup: before any barrier
+        const T bad = (T)__builtin_nan("");
+        for (int rr = 0; rr < rows; ++rr)
+            for (int c = tid; c < n; c += SF_THREADS) Mb[(long)(r0 + rr) * n + c] = cx<T>(bad, bad);
+        return;
+    }
+    if (tid == 0) {
+#pragma unroll
+        for (int p = 0; p < SF_MAXPAIRS; ++p) {
+            sg[p] = p < P.np ? P.g[p] : nullptr;
+            skl[p] = P.kl[p];
+            skr[p] = P.kr[p];
+        }
+    }
+    __syncthreads();
+    if (tid < SF_ROWS * SF_MAXPAIRS) {
+        const int rr = tid / SF_MAXPAIRS, p = tid % SF_MAXPAIRS;
+        const cx<T>* row = nullptr;
+        cx<T> wr(T(0), T(0));
+        if (rr < rows && sg[p]) {
+            const int kl = skl[p], sl = pick(E.s, kl), sr = pick(E.s, skr[p]);
+            if (sl > 0 && sr > 0) {
+                wr = rwt[(r0 + rr) * 4 + kl];
+                if (nonzero(wr)) row = (const cx<T>*)sg[p] + ((long)b * sl + clamp_row(ridx[(r0 + rr) * 4 + kl] - pick(E.o, kl), sl)) * sr;
+            }
+        }
+        srow[tid] = row;
+        swx[tid] = wr.x;
+        swy[tid] = wr.y;
+    }
+    __syncthreads();
+    for (int c = tid; c < n; c += SF_THREADS) {
+        int lc[SF_MAXBLK];
+        cx<T> wc[SF_MAXBLK];
+#pragma unroll
+        for (int k = 0; k < SF_MAXBLK; ++k) {
+            wc[k] = cx<T>(T(0), T(0));
+            lc[k] = 0;
+            if (k < nblk && E.s[k] > 0) {
+                wc[k] = conj(rwt[c * 4 + k]);
+                lc[k] = clamp_row(ridx[c * 4 + k] - E.o[k], E.s[k]);
+            }
+        }
+        for (int rr = 0; rr < rows; ++rr) {
+            cx<T> acc(T(0), T(0));
+            for (int p = 0; p < P.np; ++p) {
+                const cx<T>* row = (const cx<T>*)srow[rr * SF_MAXPAIRS + p];            // the same for every lane
+                if (!row) continue;
+                const int kr = skr[p];
+                const cx<T> w2 = pick(wc, kr);
+                if (nonzero(w2)) cfma(acc, cx<T>(swx[rr * SF_MAXPAIRS + p], swy[rr * SF_MAXPAIRS + p]) * row[pick(lc, kr)], w2);
+            }
+            Mb[(long)(r0 + rr) * n + c] = acc;
+        }
+    }
+}
+
+// gbd[2 p + q][b][m] = element (p N + m, q N + m) of T_kl G[b] T_kr^H.  grid (ceil(N / SF_THREADS), batch); a malformed off fills gbd with NaN.
+template <class T>
+__global__ __launch_bounds__(SF_THREADS) void sym_fold_pair_bd_bwd_kernel(const cx<T>* __restrict__ G, const int* __restrict__ ridx,
+                                                                          const cx<T>* __restrict__ rwt, const int* __restrict__ off, int nblk, int n,
+                                                                          int batch, int kl, int kr, cx<T>* __restrict__ gbd) {
+    const int N = n >> 1, m = blockIdx.x * SF_THREADS + threadIdx.x, b = blockIdx.y;
+    if (m >= N) return;
+    const PairExtent E = pair_extent(off, nblk, n, kl, kr);
+    const T bad = (T)__builtin_nan("");
+#pragma unroll
+    for (int pq = 0; pq < 4; ++pq) {
+        const int r = (pq >> 1) * N + m, c = (pq & 1) * N + m;
+        cx<T> v(T(0), T(0));
+        if (!E.ok) {
+            v = cx<T>(bad, bad);
+        } else if (E.nl > 0 && E.nr > 0) {
+            const cx<T> wr = rwt[r * 4 + kl], wc = conj(rwt[c * 4 + kr]);
+            if (nonzero(wr) && nonzero(wc)) {
+                const int lr = clamp_row(ridx[r * 4 + kl] - E.ol, E.nl), lc = clamp_row(ridx[c * 4 + kr] - E.oc, E.nr);
+                v = (wr * G[((long)b * E.nl + lr) * E.nr + lc]) * wc;
+            }
+        }
+        gbd[((long)pq * batch + b) * N + m] = v;
+    }
+}
+
 size_t part_bytes(int n, int batch) { return sizeof(double) * 2 * (size_t)cdiv_i(n, SF_ROWS) * (size_t)batch; }
 
 template <class T>
@@ -464,6 +610,28 @@ int sym_fold_pair_t(hipStream_t st, const cx<T>* src, int n, int batch, const in
                    sizeof(cx<T>) * (BD ? 2.0 * n * batch + blk : 17.0 * blk));
     TRX_LAUNCH((sym_fold_pair_kernel<T, BD>), dim3(cdiv_i(n, SF_ROWS), batch), dim3(SF_THREADS), 0, st, src, idx, wt, off, nblk, n, batch, kl, kr,
                out);
+    TRX_CHECK_LAUNCH();
+    return TRX_OK;
+}
+
+template <class T>
+int sym_fold_pairs_bwd_t(hipStream_t st, const PairTable& P, int n, int batch, const int* ridx, const cx<T>* rwt, const int* off, int nblk, cx<T>* gM) {
+    const double nn = (double)n * n * batch;
+    int live = 0;
+    for (int p = 0; p < P.np; ++p) live += P.g[p] != nullptr;
+    ProfScope prof(PROF_SYM_FOLD_PAIRS_BWD, st, 8.0 * 2.0 * live * nn, sizeof(cx<T>) * (1.0 + live) * nn);   // gM out, one element per pair at most
+    TRX_LAUNCH((sym_fold_pairs_bwd_kernel<T>), dim3(cdiv_i(n, SF_ROWS), batch), dim3(SF_THREADS), 0, st, P, ridx, rwt, off, nblk, n, batch, gM);
+    TRX_CHECK_LAUNCH();
+    return TRX_OK;
+}
+
+template <class T>
+int sym_fold_pair_bd_bwd_t(hipStream_t st, const cx<T>* G, int n, int batch, const int* ridx, const cx<T>* rwt, const int* off, int nblk, int kl,
+                           int kr, cx<T>* gbd) {
+    const double e = 2.0 * n * batch;                                                  // 4 N batch diagonal entries
+    ProfScope prof(PROF_SYM_FOLD_PAIR_BD_BWD, st, 8.0 * 2.0 * e, sizeof(cx<T>) * 2.0 * e);                   // one element of G in, one entry out
+    TRX_LAUNCH((sym_fold_pair_bd_bwd_kernel<T>), dim3(cdiv_i(n >> 1, SF_THREADS), batch), dim3(SF_THREADS), 0, st, G, ridx, rwt, off, nblk, n, batch,
+               kl, kr, gbd);
     TRX_CHECK_LAUNCH();
     return TRX_OK;
 }
@@ -564,4 +732,42 @@ extern "C" int trx_sym_fold_pair_bd(int dtype, const void* bd, int N, int batch,
     if (dtype == TRX_C64)
         return sym_fold_pair_t<float, true>(st, (const cx<float>*)bd, n, batch, idx, (const cx<float>*)wt, off, nblk, kl, kr, (cx<float>*)out);
     return sym_fold_pair_t<double, true>(st, (const cx<double>*)bd, n, batch, idx, (const cx<double>*)wt, off, nblk, kl, kr, (cx<double>*)out);
+}
+
+extern "C" int trx_sym_fold_pairs_backward(int dtype, const void* const* G, const int* kl, const int* kr, int npairs, int n, int batch,
+                                           const int* ridx, const void* rwt, const int* off, int nblk, void* gM, void* stream) {
+    const int rc = check_common(dtype, n, batch, nblk);
+    if (rc != TRX_OK) return rc;
+    if (npairs < 0 || npairs > SF_MAXPAIRS) return TRX_ERR_ARG;
+    if (npairs > 0 && kl && kr)
+        for (int p = 0; p < npairs; ++p)
+            if (kl[p] < 0 || kl[p] >= nblk || kr[p] < 0 || kr[p] >= nblk) return TRX_ERR_ARG;
+    if (batch == 0) return TRX_OK;
+    if ((npairs > 0 && (!G || !kl || !kr)) || !ridx || !rwt || !off || !gM) return TRX_ERR_ARG;
+    PairTable P;
+    P.np = npairs;
+    for (int p = 0; p < SF_MAXPAIRS; ++p) {
+        P.g[p] = p < npairs ? G[p] : nullptr;
+        P.kl[p] = (signed char)(p < npairs ? kl[p] : 0);
+        P.kr[p] = (signed char)(p < npairs ? kr[p] : 0);
+    }
+    hipStream_t st = trx::api_stream(stream);
+    if (dtype == TRX_C64) return sym_fold_pairs_bwd_t<float>(st, P, n, batch, ridx, (const cx<float>*)rwt, off, nblk, (cx<float>*)gM);
+    return sym_fold_pairs_bwd_t<double>(st, P, n, batch, ridx, (const cx<double>*)rwt, off, nblk, (cx<double>*)gM);
+}
+
+extern "C" int trx_sym_fold_pair_bd_backward(int dtype, const void* G, int N, int batch, const int* ridx, const void* rwt, const int* off, int nblk,
+                                             int kl, int kr, void* gbd, void* stream) {
+    if (dtype != TRX_C64 && dtype != TRX_C128) return TRX_ERR_DTYPE;
+    if (N < 1 || N > (1 << 14)) return TRX_ERR_ARG;
+    const int n = 2 * N;
+    const int rc = check_common(dtype, n, batch, nblk);
+    if (rc != TRX_OK) return rc;
+    if (kl < 0 || kl >= nblk || kr < 0 || kr >= nblk) return TRX_ERR_ARG;
+    if (batch == 0) return TRX_OK;
+    if (!G || !ridx || !rwt || !off || !gbd) return TRX_ERR_ARG;
+    hipStream_t st = trx::api_stream(stream);
+    if (dtype == TRX_C64)
+        return sym_fold_pair_bd_bwd_t<float>(st, (const cx<float>*)G, n, batch, ridx, (const cx<float>*)rwt, off, nblk, kl, kr, (cx<float>*)gbd);
+    return sym_fold_pair_bd_bwd_t<double>(st, (const cx<double>*)G, n, batch, ridx, (const cx<double>*)rwt, off, nblk, kl, kr, (cx<double>*)gbd);
 }

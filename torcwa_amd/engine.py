@@ -831,6 +831,55 @@ class Engine:
                                                  out.data_ptr(), self.stream))
         return out
 
+    @_phase("symmetry sector fold backward (trx_sym_fold_pairs_backward)")
+    def sym_fold_pairs_backward(self, grads, plan, pairs, B=None, dtype=None):
+        """gM [B,n,n] = sum_p T_kl_p G_p T_kr_p^H (include/trx.h: trx_sym_fold_pairs_backward), the adjoint of sym_fold_pair over the list
+        `pairs` of (kl, kr), at most 16.  grads: one [B, n_kl, n_kr] tensor or None per pair; None is a pair without a gradient.  B, dtype: needed
+        only when every gradient is None (the result is then all zeros)."""
+        pairs = [self._pair(plan, kl, kr) for kl, kr in pairs]
+        if len(grads) != len(pairs) or len(pairs) > 16:
+            raise ValueError(f"sym_fold_pairs_backward: {len(grads)} gradients for {len(pairs)} pairs (at most 16)")
+        live = [self._c(g) if g is not None else None for g in grads]
+        first = next((g for g in live if g is not None), None)
+        if first is not None:
+            self._check(*[g for g in live if g is not None])
+            B, dtype = first.shape[0], first.dtype
+        if B is None or dtype is None:
+            raise ValueError("sym_fold_pairs_backward: every gradient is None: give B and dtype")
+        for g, (kl, kr) in zip(live, pairs):
+            if g is not None and (tuple(g.shape) != (B, plan.sizes[kl], plan.sizes[kr]) or g.dtype != dtype):
+                raise ValueError(f"sym_fold_pairs_backward: the gradient of pair ({kl}, {kr}) must be [{B}, {plan.sizes[kl]}, {plan.sizes[kr]}] "
+                                 f"{dtype}, got {list(g.shape)} {g.dtype}")
+        n, m = plan.n, len(pairs)
+        _, _, off = plan.device(self.device, dtype)
+        ridx, rwt = plan.rows(self.device, dtype)
+        gM = torch.empty((B, n, n), dtype=dtype, device=self.device)
+        pg = (ctypes.c_void_p * max(m, 1))(*[g.data_ptr() if g is not None and g.numel() else None for g in live])
+        pl = (ctypes.c_int * max(m, 1))(*[p[0] for p in pairs])
+        pr = (ctypes.c_int * max(m, 1))(*[p[1] for p in pairs])
+        self.lib.check(self.lib.sym_fold_pairs_backward(_CODE[dtype], ctypes.addressof(pg), ctypes.addressof(pl), ctypes.addressof(pr), m, n, B,
+                                                        ridx.data_ptr(), rwt.data_ptr(), off.data_ptr(), plan.nblk, gM.data_ptr(), self.stream))
+        return gM
+
+    @_phase("symmetry sector fold backward (trx_sym_fold_pair_bd_backward)")
+    def sym_fold_pair_bd_backward(self, G, plan, kl, kr):
+        """gbd [4,B,N]: the four diagonals of T_kl G T_kr^H for G [B, n_kl, n_kr] (include/trx.h: trx_sym_fold_pair_bd_backward), the adjoint of
+        sym_fold_pair_bd."""
+        G = self._c(G)
+        self._check(G)
+        kl, kr = self._pair(plan, kl, kr)
+        if G.dim() != 3 or tuple(G.shape[1:]) != (plan.sizes[kl], plan.sizes[kr]):
+            raise ValueError(f"sym_fold_pair_bd_backward: G must be [B, {plan.sizes[kl]}, {plan.sizes[kr]}], got {list(G.shape)}")
+        B, N, dt = G.shape[0], plan.n // 2, G.dtype
+        if G.numel() == 0:                                                             # an empty block reaches no diagonal entry
+            return torch.zeros((4, B, N), dtype=dt, device=self.device)
+        _, _, off = plan.device(self.device, dt)
+        ridx, rwt = plan.rows(self.device, dt)
+        gbd = torch.empty((4, B, N), dtype=dt, device=self.device)
+        self.lib.check(self.lib.sym_fold_pair_bd_backward(_CODE[dt], G.data_ptr(), N, B, ridx.data_ptr(), rwt.data_ptr(), off.data_ptr(), plan.nblk,
+                                                          kl, kr, gbd.data_ptr(), self.stream))
+        return gbd
+
     @staticmethod
     def _pair(plan, kl, kr):
         kl, kr = int(kl), int(kr)
