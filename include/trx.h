@@ -331,6 +331,36 @@ int trx_layer_flux(int dtype, const void* W, const void* V, const void* cplus, c
                    const double* d, const double* z, int z_is_fraction, int N, int nz, int batch, double* flux, void* ws, size_t ws_bytes,
                    void* stream);
 
+/* ---- field maps for a batch (the formulas of the reference's field_xy / field_xz / field_yz, torcwa/rcwa.py:598-1112) -----------------------
+ * trx_layer_field: the Fourier coefficients of the fields inside one internal layer at nz depths, with the mode amplitudes of trx_layer_flux,
+ *   a_k = cplus_k exp(i omega kz_k z),  b_k = cminus_k exp(i omega kz_k (d - z)),  e = W (a + b),  h = V (a - b)       (n = 2N rows: x then y)
+ *   out[b,0..3,j,t] = ex_j, ey_j, hx_j, hy_j   (= e_j, e_{j+N}, h_j, h_{j+N})
+ *   out[b,4,j,t]    = ky_j hx_j - kx_j hy_j    (E_z before [eps]^-1)
+ *   out[b,5,j,t]    = kx_j ey_j - ky_j ex_j    (H_z before [mu]^-1)                                 z = z[b,t]  (z_is_fraction: z[b,t] d[b])
+ * W, V [batch,n,n] (16-byte aligned), cplus, cminus, kz [batch,n] and out [batch,6,N,nz] in `dtype` (element alignment suffices); omega, d
+ * [batch], z [batch,nz] and kx, ky [batch,N] are float64.  nz = 0 or batch = 0 returns TRX_OK without touching any buffer; batch <= 65535.
+ * Exponents, dot products and rows 4, 5 are fp64 for both dtypes; the result is rounded once, to `dtype`.  The right-hand sides are formed in
+ * LDS and never written to memory.  Traffic model: W and V are read once per tile of up to 16 depths (2 n^2 elements per point and tile; 118 MB
+ * at n = 1922 in complex128) and 6 N nz elements are written; everything else is O(n nz).  No workspace and no atomics: each output element
+ * is owned by one thread of one workgroup (32 harmonics j, i.e. rows j and j + N of W and of V), so two calls give the same bits. */
+int trx_layer_field(int dtype, const void* W, const void* V, const void* cplus, const void* cminus, const void* kz, const double* omega,
+                    const double* d, const double* z, int z_is_fraction, const double* kx, const double* ky, int N, int nz, int batch, void* out,
+                    void* stream);
+/* trx_field_synth: Fourier coefficients to space, the Bloch phases formed in the kernel,
+ *   out[b,c,iu,iv,t] = sum_m coef[b,c,m,t] exp(i omega_b (kx[b,m] u_iu + ky[b,m] v_iv))
+ * coef [batch,ncomp,N,T] and out [batch,ncomp,nu,nv T] in `dtype` (element alignment suffices); kx, ky [batch,N] and omega [batch] float64;
+ * u [nu], v [nv] float64, shared by the batch.  1 <= ncomp <= 6; either nv = 1 (a vertical cut with T depths) or T = 1 (a horizontal map), else
+ * TRX_ERR_ARG.  For a yz cut the caller swaps the roles: (ky, kx) and (y_axis, [x0]).  kx, ky are arbitrary per harmonic: any order set, any
+ * lattice.  nu = 0, nv = 0 or batch = 0 returns TRX_OK without touching any buffer; batch <= 65535, nu <= 16 * 65535.
+ * Phases and sums are fp64 for both dtypes.  All ncomp components of a point share one phase.  A map takes the phase as the product of a u table
+ * [16, 16] and a v table [16, 64] staged in LDS per chunk of 16 harmonics -- 0.08 sincos per (point, harmonic) -- and a cut stages one table
+ * [16, 8] of the whole phase; neither the [nu,N] and [N,nv] phase matrices nor (phase x coef) reach memory.  Work model: 4 real multiply-adds
+ * per (point, harmonic) for the phase product and 4 per component, 28 for six, in vector fp64; traffic: coef is read once per tile of 16 x 64
+ * points (from cache after the first) and out is written once.  Deterministic: each output element is owned by one thread, summed over m in
+ * ascending order; no workspace, no atomics. */
+int trx_field_synth(int dtype, const void* coef, const double* kx, const double* ky, const double* omega, const double* u, const double* v,
+                    int ncomp, int N, int T, int nu, int nv, int batch, void* out, void* stream);
+
 /* ---- volume integrals inside a layer (no reference counterpart; the closed form other RCWA codes offer as a layer volume integral) -------
  * trx_modal_overlap: out[b,r] = sum_{k,l} M[b,k,l] T_kl(z0, z1), (z0, z1) = zr[b,r] (z_is_fraction: times d[b]), the z integral over [z0, z1] of
  * sum_kl M_kl conj(a_k + s b_k)(a_l + s b_l) with the mode amplitudes of trx_layer_flux,

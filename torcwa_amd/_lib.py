@@ -72,6 +72,10 @@ _SIGS = {
     "trx_layer_flux_ws_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
     "trx_layer_flux": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int,
                                c_void_p, c_void_p, c_size_t, c_void_p]),
+    "trx_layer_field": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p,
+                                c_int, c_int, c_int, c_void_p, c_void_p]),
+    "trx_field_synth": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int,
+                                c_void_p, c_void_p]),
     "trx_modal_overlap_ws_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
     "trx_modal_overlap": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int,
                                   c_void_p, c_void_p, c_size_t, c_void_p]),

@@ -18,6 +18,7 @@ from . import autograd_ops as ag
 from . import lattice as _lat
 from . import symmetry as _sym
 from .blockdiag import BlockDiag2, _halfspace_V, _kz_branch, _star_bd
+from .batched_fields import BatchedFieldMixin
 from .flux import FluxMixin
 from .readout import PI_REF, ReadoutMixin  # noqa: F401  (PI_REF: part of this module's interface)
 from .sector import SectorMixin
@@ -67,7 +68,7 @@ def _propagate_coupling(mm, Cm, Cn, X1, X2, Y1, Y2):
     return C
 
 
-class BatchedRCWA(FluxMixin, VolumeMixin, ReadoutMixin, SectorMixin, SweptMixin):
+class BatchedRCWA(FluxMixin, BatchedFieldMixin, VolumeMixin, ReadoutMixin, SectorMixin, SweptMixin):
     def __init__(self, freq, order, L, *, batch=None, dtype=torch.complex64, device=None, stable_eig_grad=True,
                  avoid_Pinv_instability=False, max_Pinv_instability=0.005, precision="high", engine=None,
                  keep_coupling=True, fold_layers=False, eig_route="auto", route_hint=None, fourier_rule="laurent", nv_sigma=NV_SIGMA_DEFAULT,

@@ -576,6 +576,43 @@ class Engine:
                                            ws.data_ptr(), nws, self.stream))
         return flux
 
+    # -- field maps -----------------------------------------------------------------------------------
+    @_phase("field maps (trx_layer_field, trx_field_synth)")
+    def layer_field(self, W, V, cplus, cminus, kz, omega, d, z, kx, ky, *, z_is_fraction=False):
+        """[B,6,N,nz] Fourier coefficients (ex, ey, hx, hy, ky hx - kx hy, kx ey - ky ex) at the depths z [B,nz] of a layer (include/trx.h:
+        trx_layer_field).  W, V [B,n,n]; cplus, cminus, kz [B,n]; omega, d [B] and kx, ky [B,N] real."""
+        W, V, cplus, cminus, kz = (self._c(t) for t in (W, V, cplus, cminus, kz))
+        self._check(W, V, cplus, cminus, kz)
+        B, n, _ = W.shape
+        f64 = lambda t: self._c(t.to(device=self.device, dtype=torch.float64))
+        omega, d, z, kx, ky = f64(omega), f64(d), f64(z), f64(kx), f64(ky)
+        if tuple(V.shape) != (B, n, n) or any(tuple(t.shape) != (B, n) for t in (cplus, cminus, kz)) or omega.shape != (B,) or d.shape != (B,) \
+                or z.dim() != 2 or z.shape[0] != B or n % 2 or any(tuple(t.shape) != (B, n // 2) for t in (kx, ky)):
+            raise ValueError("layer_field: W, V [B,n,n]; cplus, cminus, kz [B,n]; omega, d [B]; z [B,nz]; kx, ky [B,n/2]")
+        nz = z.shape[1]
+        out = torch.empty((B, 6, n // 2, nz), dtype=W.dtype, device=self.device)
+        self.lib.check(self.lib.layer_field(_CODE[W.dtype], W.data_ptr(), V.data_ptr(), cplus.data_ptr(), cminus.data_ptr(), kz.data_ptr(),
+                                            omega.data_ptr(), d.data_ptr(), z.data_ptr(), int(bool(z_is_fraction)), kx.data_ptr(), ky.data_ptr(),
+                                            n // 2, nz, B, out.data_ptr(), self.stream))
+        return out
+
+    @_phase("field maps (trx_layer_field, trx_field_synth)")
+    def field_synth(self, coef, kx, ky, omega, u, v):
+        """[B,ncomp,nu,nv,T] = sum_m coef[B,ncomp,m,T] exp(i omega (kx_m u + ky_m v)) for coef [B,ncomp,N,T], kx, ky [B,N], omega [B], u [nu],
+        v [nv] (real); nv = 1 or T = 1 (include/trx.h: trx_field_synth)."""
+        coef = self._c(coef)
+        self._check(coef)
+        B, ncomp, N, T = coef.shape
+        f64 = lambda t: self._c(t.to(device=self.device, dtype=torch.float64))
+        kx, ky, omega, u, v = f64(kx), f64(ky), f64(omega), f64(u).reshape(-1), f64(v).reshape(-1)
+        if tuple(kx.shape) != (B, N) or tuple(ky.shape) != (B, N) or omega.shape != (B,):
+            raise ValueError("field_synth: coef [B,ncomp,N,T]; kx, ky [B,N]; omega [B]; u [nu]; v [nv]")
+        nu, nv = u.shape[0], v.shape[0]
+        out = torch.empty((B, ncomp, nu, nv, T), dtype=coef.dtype, device=self.device)
+        self.lib.check(self.lib.field_synth(_CODE[coef.dtype], coef.data_ptr(), kx.data_ptr(), ky.data_ptr(), omega.data_ptr(), u.data_ptr(),
+                                            v.data_ptr(), ncomp, N, T, nu, nv, B, out.data_ptr(), self.stream))
+        return out
+
     # -- volume integrals ------------------------------------------------------------------------------
     @_phase("volume integrals (trx_modal_overlap)")
     def modal_overlap(self, M, cplus, cminus, kz, omega, d, zr, s, z_is_fraction=False):

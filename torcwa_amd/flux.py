@@ -30,7 +30,8 @@ class FluxMixin:
         cdt, dev, N, B = self._cdtype, self._device, self.order_N, self.B
         orders = torch.as_tensor(orders, dtype=torch.int64, device=dev).reshape([-1, 2])
         M = orders.shape[0]
-        amp = torch.as_tensor(amplitude, device=dev).to(cdt)
+        # python scalars / lists: built directly in the compute dtype like FieldMixin.source_fourier (no fp32 detour: 0.3 would arrive as 0.3f)
+        amp = amplitude.to(device=dev, dtype=cdt) if torch.is_tensor(amplitude) else torch.as_tensor(amplitude, dtype=cdt, device=dev)
         if amp.numel() == 2 * M:
             amp = amp.reshape(1, M, 2).expand(B, M, 2)
         elif amp.numel() == 2 * M * B:
