@@ -508,7 +508,30 @@ int trx_sym_fold_pair_bd_backward(int dtype, const void* G, int N, int batch, co
  *   ws: trx_thickness_columns_ws_bytes = batch T (2 n^2 + 5 n m) elements; it scales with T: the caller chunks T.  batch * T <= 65535.
  *   Traffic of the new kernels, elements: K assembly n^2 read per point, 2 n^2 written per (point, thickness); the skinny products read their
  *   one or two n x n matrices ceil(T m / 8) times per point; everything else is O(n m) per (point, thickness).
- * Both: stream-ordered, no host synchronisation; complex64 and complex128; batch <= 65535; batch = 0 (and T = 0) returns TRX_OK without touching
+ * trx_thickness_columns_keep: trx_thickness_columns, same arguments, results and bits, that also stores the solved amplitude (c+ for direction 0,
+ *   c- for direction 1) in cp [batch,ldt,n,m], laid out like out.  It is the one forward intermediate the adjoint needs.
+ *
+ * trx_thickness_columns_backward (per chunk of T thicknesses): the adjoint of trx_thickness_columns in PyTorch's convention for holomorphic
+ *   functions (for C = A B: gA = G B^H, gB = A^H G), no atomics: every gradient element has one writer and a fixed summation order, so a
+ *   repeated call gives the same bits.  gout [batch,ldt,n,m]: the incoming gradient of out; cp: as trx_thickness_columns_keep stored it.
+ *   Outputs, each optional (null: not wanted, its work is skipped; all null: nothing at all is written):
+ *     grhoL, grhoR [batch,n,n];  gsrc [2,batch,n,m] (of src[0] and src[1]; src[1] takes a gradient from the reflection port only, zero otherwise);
+ *     gAB [2,batch,n,n];  gphase [batch,ldt,n] (written, never accumulated: a thickness belongs to one chunk);  gop: the gradient of the ONE
+ *     block of the output-side operand that the forward multiplies with (Rgt11 or Lft22): [batch,n,n] for a dense operand, its four diagonals
+ *     [4,batch,N] for a block-diagonal one, ignored for an absent one.
+ *   accumulate = 1 adds to grhoL, grhoR, gsrc, gAB and gop instead of overwriting them (the second and later chunks of the thickness axis).
+ *   With X = diag(phase_t), rho_A / rho_B = rhoL / rhoR (direction 0) or rhoR / rhoL (1), O the output block, per thickness (recomputed:
+ *   u = X cp, cs = rho_B u, w = X cs):
+ *     g~ = O^H gout (gout without O);  gO += gout g^H, g the forward's column before O;  reflection: gsrc[1] += gout
+ *     transmission: u~ = A^H g~/2, cs~ = B^H g~/2, gA += g~ u^H/2, gB += g~ cs^H/2, cp~ = 0
+ *     reflection:   cp~ = B^H g~/2, w~ = A^H g~/2, gB += g~ cp^H/2, gA += g~ w^H/2, cs~ = conj(x) w~, gx += sum_q w~ conj(cs), u~ = 0
+ *     grho_B += cs~ u^H;  u~ += rho_B^H cs~;  gx += sum_q u~ conj(cp);  cp~ += conj(x) u~
+ *     lambda = K^-H cp~ (K^H = I - (X rho_B X)^H rho_A^H: one GEMM and one LU, the forward's 1.33 n^3 again);  gsrc[0] += lambda
+ *     grho_A += lambda w^H;  mu = rho_A^H lambda;  grho_B += (conj(x) mu) u^H;  gx += sum_q mu conj(cs) + conj(cp) (rho_B^H (conj(x) mu))
+ *   info[b,t] (leading dimension ldt): the LU of K^H, written when a gradient that needs the solve is wanted (grhoL, grhoR, gsrc, gphase).
+ *   piv: int[batch*T*(n+1)] scratch.  ws: trx_thickness_columns_backward_ws_bytes = batch T (2 n^2 + 15 n m) elements.  Validation as
+ *   trx_thickness_columns; accumulate must be 0 or 1.
+ * All: stream-ordered, no host synchronisation; complex64 and complex128; batch <= 65535; batch = 0 (and T = 0) returns TRX_OK without touching
  * any buffer; TRX_ERR_ARG for a kind, direction, port, column index or m out of range or a missing pointer, TRX_ERR_WORKSPACE for a short ws. */
 size_t trx_thickness_prepare_ws_bytes(int dtype, int N, int batch);
 int trx_thickness_prepare(int dtype, const void* W, const void* V, const void* vfinv, int left_kind, const void* left, int right_kind,
@@ -518,6 +541,14 @@ size_t trx_thickness_columns_ws_bytes(int dtype, int N, int batch, int T, int m)
 int trx_thickness_columns(int dtype, const void* rhoL, const void* rhoR, const void* src, const void* AB, const void* phase, int ldt, int T,
                           int direction, int port, int left_kind, const void* left, int right_kind, const void* right, int m, int N, int batch,
                           void* out, int* piv, int* info, void* ws, size_t ws_bytes, void* stream);
+int trx_thickness_columns_keep(int dtype, const void* rhoL, const void* rhoR, const void* src, const void* AB, const void* phase, int ldt, int T,
+                               int direction, int port, int left_kind, const void* left, int right_kind, const void* right, int m, int N, int batch,
+                               void* out, void* cp, int* piv, int* info, void* ws, size_t ws_bytes, void* stream);
+size_t trx_thickness_columns_backward_ws_bytes(int dtype, int N, int batch, int T, int m);
+int trx_thickness_columns_backward(int dtype, const void* rhoL, const void* rhoR, const void* AB, const void* phase, int ldt, int T, int direction,
+                                   int port, int left_kind, const void* left, int right_kind, const void* right, int m, int N, int batch,
+                                   const void* cp, const void* gout, void* grhoL, void* grhoR, void* gsrc, void* gAB, void* gphase, void* gop,
+                                   int accumulate, int* piv, int* info, void* ws, size_t ws_bytes, void* stream);
 
 /* ---- measurement aid (no reference counterpart): HIP-event timing of the dominant kernels --------------------
  * trx_prof_enable(1) makes the instrumented launch sites record hipEvents on the launch stream.  Sampling is systematic and
@@ -529,7 +560,7 @@ int trx_thickness_columns(int dtype, const void* rhoL, const void* rhoR, const v
  * 16 trx_sym_fold (both passes); 17 trx_sym_unfold (zero fill and scatter); 18 trx_thickness_prepare (whole call); 19 - 21 the stages of
  * trx_thickness_columns, one event pair per call each: 19 K assembly and its GEMMs, 20 LU of K and the column solve, 21 amplitudes and read-out;
  * 22 trx_sym_fold_backward; 23 trx_sym_unfold_backward; 24 trx_sym_fold_pair; 25 trx_sym_fold_pair_bd; 26 trx_sym_fold_pairs_backward;
- * 27 trx_sym_fold_pair_bd_backward. */
+ * 27 trx_sym_fold_pair_bd_backward; 28 trx_thickness_columns_backward (whole call). */
 int trx_prof_enable(int on);
 int trx_prof_reset(void);
 int trx_prof_get(int tag, double* out);

@@ -95,6 +95,12 @@ _SIGS = {
     "trx_thickness_columns_ws_bytes": (c_size_t, [c_int, c_int, c_int, c_int, c_int]),
     "trx_thickness_columns": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_int,
                                       c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "trx_thickness_columns_keep": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_int,
+                                           c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "trx_thickness_columns_backward_ws_bytes": (c_size_t, [c_int, c_int, c_int, c_int, c_int]),
+    "trx_thickness_columns_backward": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_int,
+                                               c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                               c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "trx_tuning": (c_int, [c_char_p, c_int]),
     "trx_prof_enable": (c_int, [c_int]),
     "trx_prof_reset": (c_int, []),

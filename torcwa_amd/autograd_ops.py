@@ -260,3 +260,26 @@ class SymFoldPairBdFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, G):
         return ctx.engine.sym_fold_pair_bd_backward(G, ctx.plan, *ctx.pair), None, None, None, None
+
+
+class ThicknessColumnsFn(torch.autograd.Function):
+    """out [B,T,n,m] = engine.thickness_columns_keep(rho [2,B,n,n], src [2,B,n,m], AB [2,B,n,n], phase [B,T,n], op): the per-thickness step of
+    a swept solve (include/trx.h: trx_thickness_columns).  op: the output-side block, dense [B,n,n], the four diagonals [4,B,N] of a
+    block-diagonal one, or None.  The solved amplitude cp is the only forward intermediate saved; backward: ONE trx_thickness_columns_backward
+    per chunk of thicknesses, a gradient that is not needed travels as a null pointer.  No double backward."""
+
+    @staticmethod
+    def forward(ctx, rho, src, AB, phase, op, engine, direction, port, chunk):
+        out, cp = engine.thickness_columns_keep(rho, src, AB, phase, direction, port, op, chunk=chunk)
+        ctx.engine, ctx.meta = engine, (int(direction), int(port), chunk, op is not None)
+        ctx.save_for_backward(rho, AB, phase, cp, *([op] if op is not None else []))
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, gout):
+        direction, port, chunk, has_op = ctx.meta
+        rho, AB, phase, cp, *rest = ctx.saved_tensors
+        grads = ctx.engine.thickness_columns_backward(rho, AB, phase, cp, gout, direction, port, rest[0] if has_op else None,
+                                                      needs=ctx.needs_input_grad[:5], chunk=chunk)
+        return (*grads, None, None, None, None)

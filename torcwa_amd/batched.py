@@ -72,7 +72,7 @@ class BatchedRCWA(FluxMixin, BatchedFieldMixin, VolumeMixin, ReadoutMixin, Secto
     def __init__(self, freq, order, L, *, batch=None, dtype=torch.complex64, device=None, stable_eig_grad=True,
                  avoid_Pinv_instability=False, max_Pinv_instability=0.005, precision="high", engine=None,
                  keep_coupling=True, fold_layers=False, eig_route="auto", route_hint=None, fourier_rule="laurent", nv_sigma=NV_SIGMA_DEFAULT,
-                 symmetry=None, symmetry_tol=1e-6, symmetry_grad=False, symmetry_sector=False, sector_grad=False):
+                 symmetry=None, symmetry_tol=1e-6, symmetry_grad=False, symmetry_sector=False, sector_grad=False, swept_grad=False):
         check_fourier_rule(fourier_rule)
         # symmetry (extension): None | "x" | "y" | "xy" -- the caller states that every patterned layer is invariant under x -> -x (y -> -y) about
         # a plane and that kx0 = 0 (ky0 = 0) at every sweep point.  A = P Q of such a layer is then folded into 2 / 4 independent eigenproblems
@@ -99,6 +99,13 @@ class BatchedRCWA(FluxMixin, BatchedFieldMixin, VolumeMixin, ReadoutMixin, Secto
         self.sector_grad = bool(sector_grad)
         if self.sector_grad and not self.symmetry_sector:
             raise ValueError("sector_grad=True needs symmetry_sector=True")
+        # swept_grad=True (opt-in): add_layer(..., swept=True) is accepted on a differentiable stack; solve_S_parameters then restates the
+        # prepare step from the differentiable primitives and runs the per-thickness step through ThicknessColumnsFn (swept.py).  A stack
+        # without a tensor that requires grad takes the fused path, bit for bit.
+        self.swept_grad = bool(swept_grad)
+        if self.swept_grad and self.symmetry_sector:
+            raise ValueError("swept_grad=True is not available with symmetry_sector=True: add_layer(swept=True) itself is not (the thickness "
+                             "sweep works on the modes of the whole layer, a sector solve never forms them)")
         if self.symmetry_sector:
             self._check_sector(keep_coupling, avoid_Pinv_instability)
         self._sector_centres = None      # (cx, nx, cy, ny) of the first patterned layer: the one plan of the whole stack
@@ -299,7 +306,10 @@ class BatchedRCWA(FluxMixin, BatchedFieldMixin, VolumeMixin, ReadoutMixin, Secto
         autograd.  None: the field is derived from the eps grid (trx_normal_field, nv_sigma).
         swept=True: `thickness` is a sweep axis, [T] (shared by the points) or [B, T].  The layer's modes are computed once, exactly as for a
         plain layer, and solve_S_parameters returns [B, T, len(orders)] (one GEMM and one LU per thickness, include/trx.h:
-        trx_thickness_prepare / trx_thickness_columns).  At most one swept layer; needs keep_coupling=False and a non-differentiable stack."""
+        trx_thickness_prepare / trx_thickness_columns).  At most one swept layer; needs keep_coupling=False, and a non-differentiable stack
+        unless the solver was built with swept_grad=True: then gradients reach the swept thicknesses, the layer's eps / mu, every other layer's
+        tensors, freq and the incidence wave vector (one eigenproblem and one eigen-adjoint per point, trx_thickness_columns_backward per
+        thickness)."""
         eng, N, B, cdt = self.engine, self.order_N, self.B, self._cdtype
         if self.symmetry_sector:
             return self._add_layer_sector(thickness, eps, mu, normal_field, swept)
@@ -372,7 +382,7 @@ class BatchedRCWA(FluxMixin, BatchedFieldMixin, VolumeMixin, ReadoutMixin, Secto
                 del A
             kz = _kz_branch(torch.sqrt(lam), negate=True)                               # rcwa.py:1241
         if swept:
-            V = self._keep_swept_modes(P, W, kz, mu_s, E)
+            V = self._keep_swept_modes(P, W, kz, mu_s, E, diff)
             self._push_layer(P=P, Q=Q, kz_norm=kz, E_eigvec=W, H_eigvec=V, symmetry_residual=resid, **rec)
             self._swept = dict(index=self.layer_N - 1, d=d)
             if self.fold_layers:              # as a folded layer: the matrices the modes came from are not read again

@@ -118,6 +118,7 @@ extern "C" const char* trx_prof_tag_name(int tag) {
                                             "thickness_prepare", "thickness_columns:K_gemm", "thickness_columns:lu_solve", "thickness_columns:readout",
                                             "sym_fold_backward", "sym_unfold_backward",
                                             "sym_fold_pair", "sym_fold_pair_bd",
-                                            "sym_fold_pairs_backward", "sym_fold_pair_bd_backward"};
+                                            "sym_fold_pairs_backward", "sym_fold_pair_bd_backward",
+                                            "thickness_columns_backward"};
     return (tag >= 0 && tag < PROF_NTAGS) ? names[tag] : "?";
 }

@@ -19,7 +19,9 @@ enum ProfTag { PROF_GEMM_NN = 0, PROF_GEMM_OTHER = 1, PROF_QR_PREPARE = 2, PROF_
                // sector folds (symfold.hip): trx_sym_fold_pair, trx_sym_fold_pair_bd
                PROF_SYM_FOLD_PAIR = 24, PROF_SYM_FOLD_PAIR_BD = 25,
                // adjoints of the sector folds (symfold.hip): trx_sym_fold_pairs_backward, trx_sym_fold_pair_bd_backward
-               PROF_SYM_FOLD_PAIRS_BWD = 26, PROF_SYM_FOLD_PAIR_BD_BWD = 27, PROF_NTAGS = 28 };
+               PROF_SYM_FOLD_PAIRS_BWD = 26, PROF_SYM_FOLD_PAIR_BD_BWD = 27,
+               // adjoint of the thickness sweep (thickness.hip): one event pair per trx_thickness_columns_backward call
+               PROF_THICK_BACKWARD = 28, PROF_NTAGS = 29 };
 // (PROF_GEMM_*_F32: the fp32 GEMMs -- first stage of the mixed-precision eigensolver, precision="native" -- are counted apart from the fp64 ones:
 // other peak, other roofline)
 

@@ -720,6 +720,96 @@ class Engine:
         self._info(info, "thickness_columns")
         return out
 
+    def _tk_out_operand(self, op, direction, port, dt, B, n):
+        """The output-side block O of a swept solve -- None, dense [B,n,n] or the four diagonals [4,B,N] of a block-diagonal one -- as the
+        (left, right) operands of the C ABI: O sits in the block the forward reads (Rgt11, or Lft22), the other side is absent.  Returns
+        ((lk, lp), (rk, rp), objects to keep alive)."""
+        on_right = (int(direction) == 0) != (int(port) == 1)
+        if op is None:
+            return (0, None), (0, None), None
+        op = self._c(op)
+        self._check(op)
+        if tuple(op.shape) == (B, n, n) and op.dtype == dt:
+            arr = (ctypes.c_void_p * 4)(*[op.data_ptr()] * 4)
+            side, keep = (2, ctypes.addressof(arr)), (op, arr)
+        elif tuple(op.shape) == (4, B, n // 2) and op.dtype == dt:
+            full = torch.zeros((4, 4, B, n // 2), dtype=dt, device=self.device)
+            full[0 if on_right else 3] = op
+            side, keep = (1, full.data_ptr()), full
+        else:
+            raise ValueError(f"thickness sweep: the output operator is [{B}, {n}, {n}] (dense) or [4, {B}, {n // 2}] (block diagonal) of dtype {dt}, "
+                             f"got {list(op.shape)} {op.dtype}")
+        return ((0, None), side, keep) if on_right else (side, (0, None), keep)
+
+    def _tk_chunk(self, chunk, T, B):
+        chunk = T if not chunk else max(1, min(int(chunk), T))
+        return max(1, min(chunk, 65535 // B)) if B > 0 else chunk
+
+    @_phase("thickness sweep: columns (trx_thickness_columns)")
+    def thickness_columns_keep(self, rho, src, AB, phase, direction, port, op=None, chunk=None):
+        """(out, cp), both [B, T, n, m]: thickness_columns from the prepare step's tensors -- rho [2,B,n,n], src [2,B,n,m], AB [2,B,n,n] -- and
+        the output-side block `op` (see _tk_out_operand), together with the solved amplitude cp that thickness_columns_backward needs
+        (include/trx.h: trx_thickness_columns_keep)."""
+        rho, src, AB, phase = self._c(rho), self._c(src), self._c(AB), self._c(phase)
+        self._check(rho, src, AB, phase)
+        _, B, n, m = src.shape
+        N, dt, T = n // 2, rho.dtype, phase.shape[1]
+        if tuple(rho.shape) != (2, B, n, n) or tuple(AB.shape) != (2, B, n, n) or tuple(phase.shape) != (B, T, n):
+            raise ValueError(f"thickness_columns_keep: rho and AB must be [2, {B}, {n}, {n}] and phase [{B}, T, {n}], got {list(rho.shape)}, "
+                             f"{list(AB.shape)}, {list(phase.shape)}")
+        (lk, lp), (rk, rp), keep = self._tk_out_operand(op, direction, port, dt, B, n)
+        out = torch.empty((B, T, n, m), dtype=dt, device=self.device)
+        cp = torch.empty((B, T, n, m), dtype=dt, device=self.device)
+        info = self._ints(B * T)
+        chunk = self._tk_chunk(chunk, T, B)
+        esz = phase.element_size()
+        for t0 in range(0, T, chunk):
+            Tc = min(chunk, T - t0)
+            nws = self.lib.thickness_columns_ws_bytes(_CODE[dt], N, B, Tc, m)
+            ws = self._ws(nws)
+            piv = self._ints(B * Tc * (n + 1))
+            self.lib.check(self.lib.thickness_columns_keep(_CODE[dt], rho[0].data_ptr(), rho[1].data_ptr(), src.data_ptr(), AB.data_ptr(),
+                                                           phase.data_ptr() + t0 * n * esz, T, Tc, int(direction), int(port), lk, lp, rk, rp, m, N, B,
+                                                           out.data_ptr() + t0 * n * m * esz, cp.data_ptr() + t0 * n * m * esz, piv.data_ptr(),
+                                                           info.data_ptr() + 4 * t0, ws.data_ptr(), nws, self.stream))
+            del ws, piv
+        self._info(info, "thickness_columns")
+        return out, cp
+
+    @_phase("thickness sweep: columns backward (trx_thickness_columns_backward)")
+    def thickness_columns_backward(self, rho, AB, phase, cp, gout, direction, port, op=None, needs=(True,) * 5, chunk=None):
+        """(grho [2,B,n,n], gsrc [2,B,n,m], gAB [2,B,n,n], gphase [B,T,n], gop like op): the adjoint of thickness_columns_keep for the incoming
+        gradient gout [B,T,n,m] (include/trx.h: trx_thickness_columns_backward).  needs: which of the five are wanted; the others come back None
+        and their work is skipped.  Chunked over T like the forward: the first chunk writes, the later ones accumulate."""
+        rho, AB, phase, cp, gout = self._c(rho), self._c(AB), self._c(phase), self._c(cp), self._c(gout)
+        self._check(rho, AB, phase, cp, gout)
+        B, T, n, m = cp.shape
+        N, dt = n // 2, rho.dtype
+        if tuple(gout.shape) != (B, T, n, m) or tuple(phase.shape) != (B, T, n) or tuple(rho.shape) != (2, B, n, n) or tuple(AB.shape) != (2, B, n, n):
+            raise ValueError(f"thickness_columns_backward: cp and gout must be [{B}, {T}, {n}, {m}], phase [{B}, {T}, {n}], rho and AB "
+                             f"[2, {B}, {n}, {n}], got {list(gout.shape)}, {list(phase.shape)}, {list(rho.shape)}, {list(AB.shape)}")
+        (lk, lp), (rk, rp), keep = self._tk_out_operand(op, direction, port, dt, B, n)
+        new = lambda want, shape: torch.zeros(shape, dtype=dt, device=self.device) if want else None
+        grho, gsrc, gAB, gphase = new(needs[0], (2, B, n, n)), new(needs[1], (2, B, n, m)), new(needs[2], (2, B, n, n)), new(needs[3], (B, T, n))
+        gop = new(needs[4] and op is not None, tuple(op.shape) if op is not None else ())
+        p = lambda t, off=0: None if t is None else t.data_ptr() + off
+        info = self._ints(B * T)
+        chunk = self._tk_chunk(chunk, T, B)
+        esz = phase.element_size()
+        for t0 in range(0, T, chunk):
+            Tc = min(chunk, T - t0)
+            nws = self.lib.thickness_columns_backward_ws_bytes(_CODE[dt], N, B, Tc, m)
+            ws = self._ws(nws)
+            piv = self._ints(B * Tc * (n + 1))
+            self.lib.check(self.lib.thickness_columns_backward(_CODE[dt], rho[0].data_ptr(), rho[1].data_ptr(), AB.data_ptr(),
+                                                               phase.data_ptr() + t0 * n * esz, T, Tc, int(direction), int(port), lk, lp, rk, rp, m, N, B,
+                                                               cp.data_ptr() + t0 * n * m * esz, gout.data_ptr() + t0 * n * m * esz, p(grho),
+                                                               p(grho, B * n * n * esz), p(gsrc), p(gAB), p(gphase, t0 * n * esz), p(gop), int(t0 > 0),
+                                                               piv.data_ptr(), info.data_ptr() + 4 * t0, ws.data_ptr(), nws, self.stream))
+            del ws, piv
+        self._info(info, "thickness_columns_backward")
+        return grho, gsrc, gAB, gphase, gop
+
     # -- mirror-symmetry folding ------------------------------------------------------------------------
     @_phase("symmetry fold (trx_sym_fold)")
     def sym_fold(self, A, plan):

@@ -60,13 +60,14 @@ def auto_chunk(B, order, n_layers, precision, device, dtype=torch.complex64, str
     return fit if fit < 8 else fit - fit % 8
 
 
-def auto_thickness_chunk(B, T, n, m, cdtype, device):
+def auto_thickness_chunk(B, T, n, m, cdtype, device, backward=False):
     """Thicknesses per trx_thickness_columns call that fit the free HBM of `device` next to B resident points (_THICKNESS_MATRICES), with
-    _HEADROOM to spare; T when everything fits.  Raises with the numbers when not even one thickness fits."""
+    _HEADROOM to spare; T when everything fits.  Raises with the numbers when not even one thickness fits.  backward: the chunk is also the
+    one of trx_thickness_columns_backward, whose workspace holds the same two matrices and 15 skinny buffers instead of 5."""
     if device.type != "cuda":
         return T
     elem = 16 if cdtype == torch.complex128 else 8
-    per = B * ((_THICKNESS_MATRICES * n * n + 5 * n * m) * elem + 4 * (n + 1))
+    per = B * ((_THICKNESS_MATRICES * n * n + (15 if backward else 5) * n * m) * elem + 4 * (n + 1))
     free, total = torch.cuda.mem_get_info(device)
     free += torch.cuda.memory_reserved(device) - torch.cuda.memory_allocated(device)
     fit = int((free - _HEADROOM * total) // per)
