@@ -113,6 +113,47 @@ int trx_convmat_nv_orders(int dtype, int grid_is_complex, const void* grid, int 
                           double sigma, const double* h, const double* nn, void* Exx, void* Exy, void* Eyy, int* info, void* ws, size_t ws_bytes,
                           void* stream);
 
+/* ---- Fourier factorisation of vector shapes in closed form (no reference counterpart; what S4 and other design codes offer) ----------------------
+ * eps(r) = sum_G c(G) e^{+iG.r}, G = p b1 + q b2, b_i . a_j = 2 pi delta_ij, r in the coordinates of the field axes (origin at the cell corner):
+ *   c(G) = val[b,0] delta_G0 + sum_s val[b,s+1] chi_s(G),   chi_s(G) = (1 / cell_area) int_shape e^{-iG.r} d2r
+ * val[b,0] is the background and val[b,s+1] the contrast of shape s against the medium it sits in ([batch, S+1] complex128).
+ *   kind 0, ellipse   (Rx, Ry, Cx, Cy, theta): chi = (pi Rx Ry / A) 2 J1(rho) / rho e^{-iG.c}, rho = hypot(Rx G'x, Ry G'y), 1 at rho = 0
+ *   kind 1, rectangle (Wx, Wy, Cx, Cy, theta): chi = (Wx Wy / A) sinc(G'x Wx / 2) sinc(G'y Wy / 2) e^{-iG.c}, sinc t = sin t / t
+ *   kind 2, simple polygon (x0, y0, ... x_{K-1}, y_{K-1}, counter-clockwise; a clockwise list gives the negative), e_k = v_{k+1} - v_k, m_k the midpoint:
+ *           chi = (i / (A |G|^2)) sum_k (Gx e_ky - Gy e_kx) e^{-iG.m_k} sinc(G.e_k / 2) for G != 0, the shoelace area / A at G = 0
+ * with G' = (cos theta Gx + sin theta Gy, -sin theta Gx + cos theta Gy).  kind [S] and voff [S+1] are device int32: shape s owns
+ * par[b, voff[s] .. voff[s+1]-1] of the fp64 rows par [batch, npar] (5 values, or 2K for a polygon: K comes from the offsets).  recip: HOST
+ * double[4] = b1, b2.  The box coef[b, p + 2mmax, q + 2nmax] (|p| <= 2 mmax, |q| <= 2 nmax; complex128) is gathered into out [batch,N,N] by the
+ * kernel of trx_convmat_orders (mn, N, mmax, nmax and their check as there); coef = NULL keeps the box in the workspace (ws is not read when
+ * coef is given).  All arithmetic is fp64 for both dtypes: a complex64 call returns the complex128 result rounded once.  Every sinc, jinc and
+ * hat integral has a series branch for small arguments.  One thread per (b, p, q) loops over shapes and edges; a shape's parameters are staged
+ * in LDS in passes of 256 doubles.  No atomics.  Work model: one sincos per (coefficient, edge) and one j1 per (coefficient, ellipse):
+ * latency- and transcendental-bound; traffic is the box (16 B per coefficient) and the gather's output.
+ * TRX_ERR_ARG: an unknown kind, an ellipse / rectangle without exactly 5 values, a polygon with fewer than 3 vertices or an odd number of
+ * values, offsets that decrease or leave the row, cell_area <= 0, batch > 65535 (kind and voff are checked on the host: one more
+ * synchronisation of `stream`). */
+size_t trx_convmat_shapes_ws_bytes(int dtype, int batch, int N, int mmax, int nmax);
+int trx_convmat_shapes(int dtype, const int* kind, const int* voff, int S, const double* par, int npar, const void* val, const double* recip,
+                       double cell_area, int batch, const int* mn, int N, int mmax, int nmax, void* out, void* coef, void* ws, size_t ws_bytes,
+                       void* stream);
+/* Adjoint of the gather of trx_convmat_orders / trx_convmat_shapes: gbox[b, p + 2mmax, q + 2nmax] = the sum of gE[b,i,j] over the pairs with
+ * m_i - m_j = p, n_i - n_j = q (0 where the list has no such pair); gE [batch,N,N] in `dtype`, gbox complex128, sums in fp64.  A gather: a table
+ * (m, n) -> index or -1 is built on the device in ws (trx_toeplitz_sums_ws_bytes = (2mmax+1)(2nmax+1) int32), one wave per (p, q, b) reads
+ * gE[b, i(j), j] over j and ends with a fixed tree: bit-identical on repetition, every element of gE read once by the grid (each wave's reads are
+ * a diagonal: 16 B of every 64 B line, so about 4 N^2 x 16 B of traffic).  The list is checked on the host as in trx_convmat_orders and
+ * must not repeat a harmonic (TRX_ERR_ARG). */
+size_t trx_toeplitz_sums_ws_bytes(int dtype, int batch, int N, int mmax, int nmax);
+int trx_toeplitz_sums(int dtype, const void* gE, int batch, const int* mn, int N, int mmax, int nmax, void* gbox, void* ws, size_t ws_bytes,
+                      void* stream);
+/* Adjoint of the closed forms, in PyTorch's convention: gpar[b,i] = Re sum_pq conj(gbox) dc/dpar[b,i] (fp64 [batch, npar]; 0 for a slot no shape
+ * owns), gval[b,0] = gbox[b, G = 0], gval[b,s+1] = sum_pq conj(chi_s) gbox (complex128 [batch, S+1]).  A polygon vertex takes the
+ * boundary-velocity form: d(A chi)/dv_k = the sum over the two edges at v_k of n_e l_e int_0^1 t e^{-iG.(a + t (v_k - a))} dt, a the other end,
+ * n_e l_e = (e_y, -e_x); the hat integral e^{-i alpha}(e^{-i beta}(1 + i beta) - 1) / beta^2 by its series below |beta| = 1.  d/drho of
+ * 2 J1 / rho is -2 J2 / rho.  One workgroup of 256 threads per (b, parameter) and per (b, value); each thread sums its coefficients in ascending
+ * order, then a fixed tree: bit-identical on repetition, no atomics, no workspace.  Arguments and TRX_ERR_ARG as trx_convmat_shapes. */
+int trx_convmat_shapes_backward(const int* kind, const int* voff, int S, const double* par, int npar, const void* val, const double* recip,
+                                double cell_area, int batch, int mmax, int nmax, const void* gbox, double* gpar, void* gval, void* stream);
+
 /* ---- dense complex building blocks (the torch.matmul / torch.linalg.inv call sites, rcwa.py:1157-1304) -------- */
 /* C = alpha*op(A)*op(B) + beta*C, batched with element strides; alpha/beta point to HOST complex scalars.  lda / ldb / ldc >= the row length of
  * the stored operand; strideA or strideB may be 0 (one operand shared by the batch).  Only the m x n elements of each C are written: columns

@@ -8,7 +8,8 @@ built by `python torcwa_amd/csrc/build.py`).  There is no CPU fallback.
 """
 from .torch_eig import Eig
 from .geometry import geometry, lattice_geometry, rcwa_geo
-from . import lattice, materials, symmetry
+from . import lattice, materials, shapes, symmetry
+from .shapes import ShapeLayer
 from .rcwa import rcwa
 from .batched import BatchedRCWA
 from .sweep import solve_thickness_sweep
@@ -17,4 +18,4 @@ from ._lib import TrxError
 
 __version__ = "0.1.0"
 __all__ = ["Eig", "geometry", "lattice_geometry", "rcwa_geo", "rcwa", "BatchedRCWA", "solve_thickness_sweep", "Engine", "NumericalError", "TrxError", "lattice",
-           "materials", "__version__"]
+           "materials", "shapes", "ShapeLayer", "__version__"]

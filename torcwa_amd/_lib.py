@@ -39,6 +39,13 @@ _SIGS = {
     "trx_convmat_nv_orders_ws_bytes": (c_size_t, [c_int, c_int, c_int, c_int, c_int, c_int, c_int]),
     "trx_convmat_nv_orders": (c_int, [c_int, c_int, c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_int, c_int, c_double, c_void_p, c_void_p,
                                       c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "trx_convmat_shapes_ws_bytes": (c_size_t, [c_int, c_int, c_int, c_int, c_int]),
+    "trx_convmat_shapes": (c_int, [c_int, c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_double, c_int, c_void_p, c_int, c_int,
+                                   c_int, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "trx_toeplitz_sums_ws_bytes": (c_size_t, [c_int, c_int, c_int, c_int, c_int]),
+    "trx_toeplitz_sums": (c_int, [c_int, c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "trx_convmat_shapes_backward": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_double, c_int, c_int, c_int,
+                                            c_void_p, c_void_p, c_void_p, c_void_p]),
     "trx_build_pq_tensor": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p,
                                     c_void_p, c_void_p]),
     "trx_build_a_tensor_ws_bytes": (c_size_t, [c_int, c_int, c_int]),

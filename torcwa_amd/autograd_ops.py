@@ -80,6 +80,27 @@ class ConvMatOrdersFn(torch.autograd.Function):
         return g.to(gdt), None, None, None
 
 
+class ShapeConvFn(torch.autograd.Function):
+    """E = convmat_shapes(par, val) (include/trx.h: trx_convmat_shapes) of a packed shape list (shapes.ShapeLayer.pack).  The backward is the
+    adjoint of the gather (trx_toeplitz_sums) followed by the adjoint of the closed forms (trx_convmat_shapes_backward): exact derivatives with
+    respect to radii, widths, centres, rotations, polygon vertices and the permittivities, both kernels bit-reproducible.  Once differentiable."""
+
+    @staticmethod
+    def forward(ctx, par, val, packed, mn, mmax, nmax, cdtype, engine):
+        packed = packed._replace(par=par.detach(), val=val.detach())
+        ctx.meta = (packed, mn, mmax, nmax, engine, par.dtype, val.dtype)
+        return engine.convmat_shapes(packed, mn, cdtype, mmax, nmax)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, gE):
+        packed, mn, mmax, nmax, engine, pdt, vdt = ctx.meta
+        gbox = engine.toeplitz_sums(gE, mn, mmax, nmax)
+        gpar, gval = engine.convmat_shapes_backward(packed, gbox, mmax, nmax)
+        gval = gval if vdt.is_complex else torch.real(gval)
+        return gpar.to(pdt), gval.to(vdt), None, None, None, None, None, None
+
+
 def _twiddle(n, o, dev):
     """[n, 4o+1] complex128: exp(+2 pi i (q-2o) r / n) with exact integer phase reduction (the conjugate of the forward twiddle)."""
     r = torch.arange(n, device=dev, dtype=torch.int64)[:, None]

@@ -16,6 +16,7 @@ import torch
 from .engine import Engine, default_engine
 from . import autograd_ops as ag
 from . import lattice as _lat
+from . import shapes as _shapes
 from . import symmetry as _sym
 from .blockdiag import BlockDiag2, _halfspace_V, _kz_branch, _star_bd
 from .batched_fields import BatchedFieldMixin
@@ -41,7 +42,7 @@ Medium = namedtuple("Medium", "E Einv M Minv eps_s mu_s exx exy eyy mx my")
 # The per-layer record: every one of these attributes is a list with one entry per layer (None where a layer has no such thing), and
 # BatchedRCWA._push_layer is the one place that appends to them.  flux.py, volume.py, fields.py and rcwa.py index them by layer.
 #   thickness [B] (None: the swept layer, see _swept["d"]); eps_conv, mu_conv: Laurent's matrices; eps_grid, mu_grid (keep_coupling): the eps / mu
-#   handed to add_layer, by reference (a grid) or as the per-point scalar [B] (absorption_by_region); eps_conv_x / _y (fourier_rule="li" with
+#   handed to add_layer, by reference (a grid or a shapes.ShapeLayer) or as the per-point scalar [B] (absorption_by_region); eps_conv_x / _y (fourier_rule="li" with
 #   keep_coupling): Li's Ex, Ey; eps_conv_xx / _xy / _yy (fourier_rule="normal" with keep_coupling): the tensor Exx, Exy (= Eyx), Eyy;
 #   symmetry_residual: resid [B] of trx_sym_fold (the discarded part of T^H A T relative to max |A|); _sector_layers (symmetry_sector):
 #   dict(P=[P_k], Q=[Q_k]) of a patterned layer, with diff=True when they came through SymFoldPairsFn (sector_grad)
@@ -228,7 +229,7 @@ class BatchedRCWA(FluxMixin, BatchedFieldMixin, VolumeMixin, ReadoutMixin, Secto
 
     @staticmethod
     def _requires_grad(*values):
-        return torch.is_grad_enabled() and any(torch.is_tensor(v) and v.requires_grad for v in values)
+        return torch.is_grad_enabled() and any(isinstance(v, (torch.Tensor, _shapes.ShapeLayer)) and v.requires_grad for v in values)
 
     def _push_layer(self, **fields):
         """Append one layer to every per-layer list: fields[name] where given, None elsewhere."""
@@ -311,6 +312,7 @@ class BatchedRCWA(FluxMixin, BatchedFieldMixin, VolumeMixin, ReadoutMixin, Secto
         tensors, freq and the incidence wave vector (one eigenproblem and one eigen-adjoint per point, trx_thickness_columns_backward per
         thickness)."""
         eng, N, B, cdt = self.engine, self.order_N, self.B, self._cdtype
+        self._refuse_shapes(eps, mu, normal_field)
         if self.symmetry_sector:
             return self._add_layer_sector(thickness, eps, mu, normal_field, swept)
         if swept:
@@ -393,6 +395,20 @@ class BatchedRCWA(FluxMixin, BatchedFieldMixin, VolumeMixin, ReadoutMixin, Secto
                          symmetry_residual=resid, **rec)
         self._fold_last_layer()
 
+    def _refuse_shapes(self, eps, mu, normal_field):
+        """What a ShapeLayer cannot be combined with, each refused by name (DESIGN.md section 8 lists them as follow-ups)."""
+        if isinstance(mu, _shapes.ShapeLayer):
+            raise ValueError("a ShapeLayer cannot be given as mu: vector shapes describe the permittivity only")
+        if not isinstance(eps, _shapes.ShapeLayer):
+            return
+        if self.fourier_rule != "laurent":
+            raise ValueError(f'a ShapeLayer needs fourier_rule="laurent", got {self.fourier_rule!r}: Li\'s rule and the normal-vector rule are '
+                             "built from grids")
+        if self.symmetry is not None or self.symmetry_sector:
+            raise ValueError("a ShapeLayer cannot be combined with symmetry= / symmetry_sector=True: the mirror is detected from grids")
+        if normal_field is not None:
+            raise ValueError("a ShapeLayer cannot be combined with add_layer(normal_field=...): the normal-vector rule is built from grids")
+
     def _refuse_normal_field(self, normal_field):
         if normal_field is not None:
             raise ValueError("symmetry= cannot be combined with add_layer(normal_field=...): a caller-supplied field is not checked for the mirror; "
@@ -417,6 +433,11 @@ class BatchedRCWA(FluxMixin, BatchedFieldMixin, VolumeMixin, ReadoutMixin, Secto
             if homog:
                 s = self._bvec(v)
                 return s[:, None, None] * eye, (1 / s)[:, None, None] * eye, s
+            if isinstance(v, _shapes.ShapeLayer):      # closed-form coefficients; the rectangle of `order` and an order list both as mn
+                packed = v.pack(self._lattice, self.B, self._device)
+                if diff:
+                    return ag.ShapeConvFn.apply(packed.par, packed.val, packed, self._mn_dev, self._mmax, self._nmax, cdt, eng), None, None
+                return eng.convmat_shapes(packed, self._mn_dev, cdt, self._mmax, self._nmax), None, None
             g = self._grid(v)
             if self._general:
                 if diff:
@@ -711,6 +732,8 @@ class BatchedRCWA(FluxMixin, BatchedFieldMixin, VolumeMixin, ReadoutMixin, Secto
     def _is_homogeneous(self, v):
         if isinstance(v, (float, complex)):
             return True
+        if isinstance(v, _shapes.ShapeLayer):
+            return False
         if isinstance(v, int):                     # the reference raises AttributeError here (rcwa.py:156)
             raise AttributeError("'int' object has no attribute 'dim'")
         t = torch.as_tensor(v)

@@ -203,5 +203,7 @@ int lu_solve_right(hipStream_t s, const cx<T>* LU, int lda, long sA, int n, cons
 int orders_check(hipStream_t s, const int* mn, int N, int mmax, int nmax);
 int convmat_orders_checked(hipStream_t s, int dtype, int cplx, const void* grid, int batch, int n1, int n2, const int* mn, int N, int mmax,
                            int nmax, void* out, void* ws);
+// the gather alone: out[b,i,j] = coef[b, m_i-m_j+2mmax, n_i-n_j+2nmax] from a finished complex128 box (list already checked)
+int orders_gather(hipStream_t s, int dtype, const cx<double>* coef, const int* mn, int N, int mmax, int nmax, int batch, void* out);
 
 }  // namespace trx

@@ -134,16 +134,10 @@ __global__ __launch_bounds__(256) void orders_gather_kernel(const zc* __restrict
     }
 }
 
+// the gather of a finished coefficient box [batch, 4mmax+1, 4nmax+1] (trx_convmat_orders after its DFT; trx_convmat_shapes after its closed forms)
 template <class T>
-int convmat_orders_t(int cplx, const void* grid, int batch, int n1, int n2, const int* mn, int N, int mmax, int nmax, void* out, void* ws,
-                     hipStream_t s) {
+int orders_gather_t(hipStream_t s, const zc* coef, const int* mn, int N, int mmax, int nmax, int batch, void* out) {
     const int nq = 4 * nmax + 1, np = 4 * mmax + 1;
-    zc* T1 = reinterpret_cast<zc*>(ws);
-    zc* coef = T1 + (long)batch * n1 * nq;
-    const size_t sm1 = sizeof(zc) * 2 * (size_t)n2, sm2 = sizeof(zc) * 2 * (size_t)n1;
-    if (cplx) TRX_LAUNCH((dft_rows_kernel<T, true>), dim3(n1, batch), dim3(128), sm1, s, (const T*)grid, n1, n2, nmax, T1);
-    else      TRX_LAUNCH((dft_rows_kernel<T, false>), dim3(n1, batch), dim3(128), sm1, s, (const T*)grid, n1, n2, nmax, T1);
-    TRX_LAUNCH(dft_cols_kernel, dim3(nq, batch), dim3(128), sm2, s, (const zc*)T1, n1, n2, mmax, nmax, coef);
     const size_t box = sizeof(zc) * (size_t)np * nq;
     const dim3 g(cdiv_i(N, ORD_ROWS), batch), blk(N >= 256 ? 256 : (N > 64 ? 128 : 64));
     if (box <= ORD_LDS_MAX) {
@@ -155,7 +149,25 @@ int convmat_orders_t(int cplx, const void* grid, int batch, int n1, int n2, cons
     TRX_CHECK_LAUNCH();
     return TRX_OK;
 }
+
+template <class T>
+int convmat_orders_t(int cplx, const void* grid, int batch, int n1, int n2, const int* mn, int N, int mmax, int nmax, void* out, void* ws,
+                     hipStream_t s) {
+    const int nq = 4 * nmax + 1;
+    zc* T1 = reinterpret_cast<zc*>(ws);
+    zc* coef = T1 + (long)batch * n1 * nq;
+    const size_t sm1 = sizeof(zc) * 2 * (size_t)n2, sm2 = sizeof(zc) * 2 * (size_t)n1;
+    if (cplx) TRX_LAUNCH((dft_rows_kernel<T, true>), dim3(n1, batch), dim3(128), sm1, s, (const T*)grid, n1, n2, nmax, T1);
+    else      TRX_LAUNCH((dft_rows_kernel<T, false>), dim3(n1, batch), dim3(128), sm1, s, (const T*)grid, n1, n2, nmax, T1);
+    TRX_LAUNCH(dft_cols_kernel, dim3(nq, batch), dim3(128), sm2, s, (const zc*)T1, n1, n2, mmax, nmax, coef);
+    return orders_gather_t<T>(s, coef, mn, N, mmax, nmax, batch, out);
+}
 }  // namespace
+
+int orders_gather(hipStream_t s, int dtype, const cx<double>* coef, const int* mn, int N, int mmax, int nmax, int batch, void* out) {
+    if (dtype == TRX_C64) return orders_gather_t<float>(s, coef, mn, N, mmax, nmax, batch, out);
+    return orders_gather_t<double>(s, coef, mn, N, mmax, nmax, batch, out);
+}
 
 int orders_check(hipStream_t s, const int* mn, int N, int mmax, int nmax) {
     std::vector<int> h((size_t)2 * N);

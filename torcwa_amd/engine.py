@@ -157,6 +157,60 @@ class Engine:
                                                ws.data_ptr(), nws, self.stream))
         return out
 
+    def _shape_args(self, packed):
+        """The device operands of a packed shape list (shapes.ShapeLayer.pack): kind [S], voff [S+1] int32, par [B, npar] fp64, val [B, S+1]
+        complex128, and the host double[4] of the reciprocal vectors."""
+        kind = self._c(packed.kind.to(device=self.device, dtype=torch.int32))
+        voff = self._c(packed.voff.to(device=self.device, dtype=torch.int32))
+        par = self._c(packed.par.detach().to(device=self.device, dtype=torch.float64))
+        val = self._c(packed.val.detach().to(device=self.device, dtype=torch.complex128))
+        recip = (ctypes.c_double * 4)(*[float(v) for v in packed.recip])
+        return kind, voff, par, val, recip
+
+    @_phase("assembly (convolution matrices, E^-1, A = PQ)")
+    def convmat_shapes(self, packed, mn, dtype, mmax=None, nmax=None, want_coef=False):
+        """Packed vector shapes and an [N,2] harmonic list -> [B,N,N] convolution matrix from the closed-form Fourier coefficients
+        (include/trx.h: trx_convmat_shapes).  want_coef: also return the complex128 box [B, 4mmax+1, 4nmax+1]."""
+        kind, voff, par, val, recip = self._shape_args(packed)
+        B, npar = par.shape
+        mn, N, mmax, nmax = self._orders(mn, mmax, nmax)
+        out = torch.empty((B, N, N), dtype=dtype, device=self.device)
+        coef = torch.empty((B, 4 * mmax + 1, 4 * nmax + 1), dtype=torch.complex128, device=self.device) if want_coef else None
+        nws = self.lib.convmat_shapes_ws_bytes(_CODE[dtype], B, N, mmax, nmax)
+        ws = self._ws(nws)
+        self.lib.check(self.lib.convmat_shapes(_CODE[dtype], kind.data_ptr(), voff.data_ptr(), int(kind.numel()), par.data_ptr(), npar,
+                                               val.data_ptr(), ctypes.addressof(recip), float(packed.cell_area), B, mn.data_ptr(), N, mmax, nmax,
+                                               out.data_ptr(), coef.data_ptr() if want_coef else None, ws.data_ptr(), nws, self.stream))
+        return (out, coef) if want_coef else out
+
+    @_phase("assembly (convolution matrices, E^-1, A = PQ)")
+    def toeplitz_sums(self, gE, mn, mmax=None, nmax=None):
+        """Adjoint of the Toeplitz gather: [B,N,N] -> the complex128 box [B, 4mmax+1, 4nmax+1] of diagonal sums (trx_toeplitz_sums)."""
+        self._check(gE)
+        gE = self._c(gE)
+        B = gE.shape[0]
+        mn, N, mmax, nmax = self._orders(mn, mmax, nmax)
+        gbox = torch.empty((B, 4 * mmax + 1, 4 * nmax + 1), dtype=torch.complex128, device=self.device)
+        nws = self.lib.toeplitz_sums_ws_bytes(_CODE[gE.dtype], B, N, mmax, nmax)
+        ws = self._ws(nws)
+        self.lib.check(self.lib.toeplitz_sums(_CODE[gE.dtype], gE.data_ptr(), B, mn.data_ptr(), N, mmax, nmax, gbox.data_ptr(), ws.data_ptr(), nws,
+                                              self.stream))
+        return gbox
+
+    @_phase("assembly (convolution matrices, E^-1, A = PQ)")
+    def convmat_shapes_backward(self, packed, gbox, mmax, nmax):
+        """(gpar [B, npar] fp64, gval [B, S+1] complex128) from the gradient of the coefficient box (trx_convmat_shapes_backward)."""
+        kind, voff, par, val, recip = self._shape_args(packed)
+        B, npar = par.shape
+        S = int(kind.numel())
+        gbox = self._c(gbox.to(torch.complex128))
+        gpar = torch.empty((B, npar), dtype=torch.float64, device=self.device)
+        gval = torch.empty((B, S + 1), dtype=torch.complex128, device=self.device)
+        self.lib.check(self.lib.convmat_shapes_backward(kind.data_ptr(), voff.data_ptr(), S, par.data_ptr(), npar, val.data_ptr(),
+                                                        ctypes.addressof(recip), float(packed.cell_area), B, int(mmax), int(nmax),
+                                                        gbox.data_ptr(), gpar.data_ptr(), gval.data_ptr(), self.stream))
+        return gpar, gval
+
     @_phase("assembly (convolution matrices, E^-1, A = PQ)")
     def convmat_li(self, grid, ox, oy, dtype, keep_inverses=False):
         """[B,nx,ny] grid -> (Ex, Ey) [B,N,N], Li's inverse-rule convolution matrices of the x and y field components (include/trx.h:

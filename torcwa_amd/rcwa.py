@@ -8,6 +8,7 @@ import torch
 
 from .batched import BatchedRCWA, NV_SIGMA_DEFAULT, PI_REF
 from .fields import FieldMixin
+from .shapes import ShapeLayer
 
 pi = PI_REF
 
@@ -62,7 +63,7 @@ class rcwa(FieldMixin):
     def add_layer(self, thickness, eps=1., mu=1., normal_field=None):
         # normal_field (extension, fourier_rule="normal" only): (Nx, Ny) grids of a caller-supplied in-plane field (BatchedRCWA.add_layer)
         def prep(v):
-            if isinstance(v, (float, complex)):
+            if isinstance(v, (float, complex, ShapeLayer)):
                 return v
             # the reference tests v.dim() directly (python ints raise AttributeError there, rcwa.py:156)
             if v.dim() == 0 or (v.dim() == 1 and v.shape[0] == 1):

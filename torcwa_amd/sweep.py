@@ -14,6 +14,7 @@ import torch
 
 from .batched import NV_SIGMA_DEFAULT, BatchedRCWA, check_fourier_rule
 from .engine import default_engine
+from .shapes import ShapeLayer
 from .memory import auto_chunk, auto_thickness_chunk  # noqa: F401  (the HBM model: re-exported, the benchmark and the tests take it from here)
 
 _DATA = os.path.join(os.path.dirname(os.path.abspath(__file__)), "data")
@@ -112,6 +113,8 @@ def _slice(v, lo, hi, B):
     (a 128 x 128 grid in a 128-point sweep is not a per-point quantity)."""
     if torch.is_tensor(v) and v.dim() in (1, 3) and v.shape[0] == B:
         return v[lo:hi]
+    if isinstance(v, ShapeLayer) and v.batch == B:          # per-point shape parameters are cut, shared ones kept
+        return v.slice(lo, hi)
     return v
 
 
@@ -248,6 +251,9 @@ def solve_single_layer_sweep(freq, eps_grids, thickness, order, L, **kw):
               sweeps on two threads 18.3 layer-solves/s against 33.6, and 28.9 - 31.3 with CU-masked streams that keep the other half's GEMM
               grids off a reserved set of compute units: profiles/r06_ab/cumask.txt).
     """
+    if isinstance(eps_grids, ShapeLayer):            # vector shapes carry no device of their own: freq goes to the engine's, as to a grid's
+        eng = kw.get("engine") or default_engine()
+        return solve_stack_sweep(freq.to(eng.device), [(thickness, eps_grids)], order, L, **kw)
     return solve_stack_sweep(freq.to(eps_grids.device), [(thickness, eps_grids)], order, L, **kw)
 
 

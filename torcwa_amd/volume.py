@@ -19,6 +19,7 @@ import operator
 import torch
 
 from . import autograd_ops as ag
+from .shapes import ShapeLayer
 
 
 def _phi(x):
@@ -203,6 +204,12 @@ class VolumeMixin:
         self._flux_ready()
         l = self._vol_layer(layer_num)
         eps, mu = self.eps_grid[l], self.mu_grid[l]
+        if isinstance(eps, ShapeLayer):              # masks stay grids: the layer's Im(eps) is sampled on theirs (hard edges, the DFT's positions)
+            if masks is None:
+                raise ValueError("absorption_by_region of a ShapeLayer takes grid masks (ShapeLayer.rasterise gives eps on any grid); "
+                                 "absorption() has the whole layer")
+            shp = tuple(torch.as_tensor(masks).shape[-2:])
+            eps = eps.rasterise(self._lattice[0], self._lattice[1], shp[0], shp[1], device=self._device)
         eps_h, mu_h = self._is_homogeneous(eps), self._is_homogeneous(mu)
         zr = self._vol_ranges(l, z_range)
         m4 = None
