@@ -154,6 +154,41 @@ int trx_toeplitz_sums(int dtype, const void* gE, int batch, const int* mn, int N
 int trx_convmat_shapes_backward(const int* kind, const int* voff, int S, const double* par, int npar, const void* val, const double* recip,
                                 double cell_area, int batch, int mmax, int nmax, const void* gbox, double* gpar, void* gval, void* stream);
 
+/* ---- the normal-vector rule on vector shapes -------------------------------------------------------------------------------------------------
+ * trx_shape_normal_field: nn[b] = (Nx^2, Nx Ny, Ny^2) ([batch,3,n1,n2] fp64) of the normal field of a shape list, sampled at
+ * r = (i/n1) a1 + (j/n2) a2 (the DFT's positions, no half-pixel shift).  kind, voff, S, par, npar as trx_convmat_shapes (same host check and
+ * TRX_ERR_ARG cases); lattice: HOST double[4] = a1, a2 (finite, non-zero area).  Every primitive -- an ellipse, or one edge of a polygon (a
+ * rectangle (Wx, Wy, C, theta) is its 4-gon C + R(theta)(-+Wx/2, -+Wy/2), counter-clockwise from (-,-)) -- contributes in each of the nine
+ * images r' = r - p a1 - q a2, p, q in {-1, 0, 1}:
+ *   ellipse (Rx, Ry, c, theta): (u, w) = R(-theta)(r' - c), f = hypot(u/Rx, w/Ry), delta = |f - 1| min(Rx, Ry), g = R(theta)(u/Rx^2, w/Ry^2),
+ *           n = g/|g|; no contribution when |g| = 0
+ *   edge a -> b, e = b - a, tau = (r' - a).e/|e|^2:  0 < tau < 1: n = (e_y, -e_x)/|e|, delta = |(r' - a).n|;  otherwise v = a (tau <= 0) or b:
+ *           delta = |r' - v|, n = (r' - v)/delta; no contribution when delta = 0 (the two branches are continuous across tau = 0 and 1)
+ *   J = sum n n^T / (delta^2 + eta^2)^2, eta^2 = 1e-12 |a1 x a2|, over all primitives and images, nested shapes included
+ * and the direction is trx_normal_field's: d = Jxx - Jyy, o = 2 Jxy, r = hypot(d, o); where r > 1e-3 (Jxx + Jyy): (1 + d/r)/2, o/(2r),
+ * (1 - d/r)/2; elsewhere 0 (Laurent's rule locally: a disk's centre, exact mirror lines far from any boundary).  A blend, not a
+ * nearest-boundary choice: no tie lines, and on a mirror-symmetric structure the images cancel in Jxy.  One thread per sample, lanes along
+ * n2, grid (ceil(n1 n2 / 256), batch); parameters staged in LDS in passes of 256 doubles; the sum runs shapes ascending, images p outer and q
+ * inner, edges ascending: bit-identical on repetition.  No workspace, no atomics, all fp64.  Work model: 9 (ellipses + edges) short
+ * evaluations per sample, latency- and divide-bound; 24 B written per sample.  n1, n2 <= 2048 (else TRX_ERR_UNSUPPORTED), batch <= 65535.
+ *
+ * trx_convmat_nv_shapes: the tensor of trx_convmat_nv_orders for a shape list.  [eps] and [1/eps] are the closed-form box of
+ * trx_convmat_shapes gathered by trx_convmat_orders' kernel, once with val and once with rval ([batch, S+1] complex128, the reciprocal values:
+ * rval[b,0] = 1/eps_background, rval[b,s+1] = 1/eps_s - 1/eps_host); only the three smooth products are sampled: nn ([batch,3,n1,n2] fp64,
+ * the caller's) or NULL = trx_shape_normal_field on n1 x n2 into the workspace (lattice is read only then); their matrices come from the
+ * pruned DFT and gather of trx_convmat_orders.  Then the tail of trx_convmat_nv_orders: [1/eps]^-1 by trx_inverse in complex128, D, the six
+ * GEMMs.  recip, cell_area, mn, N, mmax, nmax as trx_convmat_shapes.  info[batch] (device): 0 ok; 1 a val / rval entry is not finite or a
+ * background entry is zero (a medium with eps zero or non-finite); 2 [1/eps] is singular.  An all-zero nn returns Exx = Eyy = the out of
+ * trx_convmat_shapes bit for bit and Exy = 0.  Requires n1 > 2 mmax, n2 > 2 nmax (the bound of trx_convmat_orders; the box of the products
+ * reaches +-2 mmax, so a grid with n1 <= 4 mmax aliases its outer coefficients -- the Python layer asks for n1 > 4 mmax), n1, n2 <= 2048
+ * (TRX_ERR_UNSUPPORTED) and 3 batch <= 65535 (TRX_ERR_ARG).  All arithmetic is fp64 for both dtypes. */
+int trx_shape_normal_field(const int* kind, const int* voff, int S, const double* par, int npar, const double* lattice, int batch, int n1, int n2,
+                           double* nn, void* stream);
+size_t trx_convmat_nv_shapes_ws_bytes(int dtype, int batch, int n1, int n2, int N, int mmax, int nmax);
+int trx_convmat_nv_shapes(int dtype, const int* kind, const int* voff, int S, const double* par, int npar, const void* val, const void* rval,
+                          const double* recip, double cell_area, const double* lattice, int batch, int n1, int n2, const int* mn, int N, int mmax,
+                          int nmax, const double* nn, void* Exx, void* Exy, void* Eyy, int* info, void* ws, size_t ws_bytes, void* stream);
+
 /* ---- dense complex building blocks (the torch.matmul / torch.linalg.inv call sites, rcwa.py:1157-1304) -------- */
 /* C = alpha*op(A)*op(B) + beta*C, batched with element strides; alpha/beta point to HOST complex scalars.  lda / ldb / ldc >= the row length of
  * the stored operand; strideA or strideB may be 0 (one operand shared by the batch).  Only the m x n elements of each C are written: columns

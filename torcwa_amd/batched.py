@@ -31,6 +31,11 @@ FOURIER_RULES = ("laurent", "li", "normal")
 # fourier_rule="normal": default width (grid cells) of the Gaussian that smooths the structure tensor of a grid into the normal-vector field
 # (include/trx.h: trx_normal_field); chosen by the CPU study in profiles/normal_vector.txt
 NV_SIGMA_DEFAULT = 6.0
+# fourier_rule="normal" on a shapes.ShapeLayer: the grid (an int or (n1, n2)) on which the three smooth products of the layer's normal field are
+# sampled (include/trx.h: trx_shape_normal_field).  128, 256 and 512 give the same digits at orders [5,5] .. [9,9] for a disk and an ellipse of
+# eps = 12, and 256 vs 512 differ by < 1e-5 at [13,13] (profiles/shape_nv_study.txt).  The keyword itself defaults to None -- the rule on shapes
+# is opt-in, so that a solver built as before behaves as before -- and this is the value to pass: shape_nv_grid=SHAPE_NV_GRID_DEFAULT.
+SHAPE_NV_GRID_DEFAULT = 256
 
 
 # The factorised medium of one layer: Laurent's E, M and their inverses (None until needed; M = Minv = None for a lean layer, see
@@ -73,7 +78,8 @@ class BatchedRCWA(FluxMixin, BatchedFieldMixin, VolumeMixin, ReadoutMixin, Secto
     def __init__(self, freq, order, L, *, batch=None, dtype=torch.complex64, device=None, stable_eig_grad=True,
                  avoid_Pinv_instability=False, max_Pinv_instability=0.005, precision="high", engine=None,
                  keep_coupling=True, fold_layers=False, eig_route="auto", route_hint=None, fourier_rule="laurent", nv_sigma=NV_SIGMA_DEFAULT,
-                 symmetry=None, symmetry_tol=1e-6, symmetry_grad=False, symmetry_sector=False, sector_grad=False, swept_grad=False):
+                 symmetry=None, symmetry_tol=1e-6, symmetry_grad=False, symmetry_sector=False, sector_grad=False, swept_grad=False,
+                 shape_nv_grid=None):
         check_fourier_rule(fourier_rule)
         # symmetry (extension): None | "x" | "y" | "xy" -- the caller states that every patterned layer is invariant under x -> -x (y -> -y) about
         # a plane and that kx0 = 0 (ky0 = 0) at every sweep point.  A = P Q of such a layer is then folded into 2 / 4 independent eigenproblems
@@ -122,6 +128,10 @@ class BatchedRCWA(FluxMixin, BatchedFieldMixin, VolumeMixin, ReadoutMixin, Secto
         self.nv_sigma = float(nv_sigma)
         if not (0.0 <= self.nv_sigma <= 256.0):
             raise ValueError(f"nv_sigma must lie in [0, 256] grid cells, got {nv_sigma!r}")
+        # a ShapeLayer under fourier_rule="normal": [eps] and [1/eps] in closed form, the field of the shape list sampled on this grid
+        # (trx_convmat_nv_shapes) unless add_layer(normal_field=...) supplies one on a grid of its own
+        # None (the default): a ShapeLayer without a supplied field stays refused under this rule, as before the rule reached shapes
+        self.shape_nv_grid = None if shape_nv_grid is None else _shapes.nv_grid(shape_nv_grid)
         if dtype != torch.complex64 and dtype != torch.complex128:                      # rcwa.py:37-41
             warnings.warn("Invalid simulation data type. Set as torch.complex64.", UserWarning)
             dtype = torch.complex64
@@ -304,7 +314,10 @@ class BatchedRCWA(FluxMixin, BatchedFieldMixin, VolumeMixin, ReadoutMixin, Secto
     def add_layer(self, thickness, eps=1., mu=1., normal_field=None, *, swept=False):  # rcwa.py:146-170
         """normal_field (fourier_rule="normal" only): (Nx, Ny), each [nx, ny] or [B, nx, ny] on the eps grid, a caller-supplied in-plane field
         for the normal-vector method (e.g. the analytic radial field of a disk), used as given (not normalised) and treated as constant by
-        autograd.  None: the field is derived from the eps grid (trx_normal_field, nv_sigma).
+        autograd.  None: the field is derived from the eps grid (trx_normal_field, nv_sigma).  With eps a ShapeLayer the grids may have any
+        size n1 > 2 mmax, n2 > 2 nmax (at most 2048), sampled at (i / n1) a1 + (j / n2) a2 like ShapeLayer.rasterise; None: the blended field
+        of the shape list on shape_nv_grid (trx_shape_normal_field); one tensor [3, n1, n2] or [B, 3, n1, n2] is taken as the
+        products (Nx^2, Nx Ny, Ny^2) themselves, as shapes.normal_products returns them.
         swept=True: `thickness` is a sweep axis, [T] (shared by the points) or [B, T].  The layer's modes are computed once, exactly as for a
         plain layer, and solve_S_parameters returns [B, T, len(orders)] (one GEMM and one LU per thickness, include/trx.h:
         trx_thickness_prepare / trx_thickness_columns).  At most one swept layer; needs keep_coupling=False, and a non-differentiable stack
@@ -401,13 +414,16 @@ class BatchedRCWA(FluxMixin, BatchedFieldMixin, VolumeMixin, ReadoutMixin, Secto
             raise ValueError("a ShapeLayer cannot be given as mu: vector shapes describe the permittivity only")
         if not isinstance(eps, _shapes.ShapeLayer):
             return
-        if self.fourier_rule != "laurent":
-            raise ValueError(f'a ShapeLayer needs fourier_rule="laurent", got {self.fourier_rule!r}: Li\'s rule and the normal-vector rule are '
-                             "built from grids")
+        if self.fourier_rule == "li":
+            raise ValueError('a ShapeLayer needs fourier_rule="laurent" or "normal", got \'li\': the per-row inverses of Li\'s rule are built '
+                             "from grids")
         if self.symmetry is not None or self.symmetry_sector:
             raise ValueError("a ShapeLayer cannot be combined with symmetry= / symmetry_sector=True: the mirror is detected from grids")
-        if normal_field is not None:
-            raise ValueError("a ShapeLayer cannot be combined with add_layer(normal_field=...): the normal-vector rule is built from grids")
+        if self.fourier_rule == "normal" and self.shape_nv_grid is None and normal_field is None:
+            # opt-in: a solver built without a field grid keeps refusing shapes under this rule, as it did before the rule reached them
+            raise ValueError('a ShapeLayer needs fourier_rule="laurent", or under fourier_rule="normal" a grid for the products of its normal '
+                             f"field: shape_nv_grid= (an int or (n1, n2); {SHAPE_NV_GRID_DEFAULT} is the measured choice, SHAPE_NV_GRID_DEFAULT) "
+                             "or add_layer(normal_field=...)")
 
     def _refuse_normal_field(self, normal_field):
         if normal_field is not None:
@@ -459,6 +475,15 @@ class BatchedRCWA(FluxMixin, BatchedFieldMixin, VolumeMixin, ReadoutMixin, Secto
 
         def conv_nv(v):
             """(Exx, Exy, Eyy) of a patterned eps grid with the normal-vector rule."""
+            if isinstance(v, _shapes.ShapeLayer):      # closed-form [eps], [1/eps]; only the field's products are sampled (both lattice paths)
+                packed = v.pack(self._lattice, self.B, self._device)
+                rval = v.reciprocal_values(self.B, self._device)
+                nn, (n1, n2) = self._shape_nv_products(normal_field)
+                if diff:
+                    if nn is None:             # the field derived from the shape list is a constant of the differentiable path (detached)
+                        nn = eng.shape_normal_field(packed, self._lattice, n1, n2)
+                    return self._nv_tensor_shapes_torch(packed, rval, nn)
+                return eng.convmat_nv_shapes(packed, rval, self._lattice, self._mn_dev, cdt, n1, n2, nn=nn, mmax=self._mmax, nmax=self._nmax)
             g = self._grid(v)
             nn = self._nv_products(g, normal_field)
             if self._general:
@@ -589,6 +614,45 @@ class BatchedRCWA(FluxMixin, BatchedFieldMixin, VolumeMixin, ReadoutMixin, Secto
             raise ValueError(f"normal_field components must be {list(shp)} grids like eps, got {list(Nx.shape)} and {list(Ny.shape)}")
         Nx, Ny = Nx.expand(self.B, -1, -1), Ny.expand(self.B, -1, -1)
         return torch.stack((Nx * Nx, Nx * Ny, Ny * Ny), dim=1).contiguous()
+
+    def _shape_nv_products(self, normal_field):
+        """(nn, (n1, n2)) for a ShapeLayer: the [B,3,n1,n2] float64 products of a caller-supplied field on its own grid, or None and
+        shape_nv_grid (the library samples the field of the shape list).  ValueError for a grid the order set does not fit on."""
+        def fits(n1, n2, factor, what):
+            if n1 <= factor * self._mmax or n2 <= factor * self._nmax or max(n1, n2) > 2048:
+                raise ValueError(f"{what} ({n1}, {n2}) is too small for the order set: it needs n1 > {factor * self._mmax}, n2 > "
+                                 f"{factor * self._nmax} ({factor} x the largest |m|, |n|) and at most 2048 points a side")
+        if normal_field is None:
+            # the box of the products reaches +-2 mmax: on fewer than 4 mmax + 1 points its outer coefficients would alias
+            fits(*self.shape_nv_grid, 4, "shape_nv_grid")
+            return None, self.shape_nv_grid
+        if torch.is_tensor(normal_field):             # the products themselves, as shapes.normal_products returns them
+            nn = normal_field.detach().to(device=self._device, dtype=torch.float64)
+            if nn.dim() not in (3, 4) or nn.shape[-3] != 3 or (nn.dim() == 4 and nn.shape[0] != self.B):
+                raise ValueError(f"normal_field products of a ShapeLayer must be [3, n1, n2] or [{self.B}, 3, n1, n2], got {list(nn.shape)}")
+            fits(int(nn.shape[-2]), int(nn.shape[-1]), 2, "the normal_field grid")
+            return nn.expand(self.B, -1, -1, -1).contiguous(), (int(nn.shape[-2]), int(nn.shape[-1]))
+        if len(normal_field) != 2:
+            raise ValueError("normal_field is (Nx, Ny)")
+        Nx, Ny = (torch.as_tensor(t, device=self._device).detach().to(torch.float64) for t in normal_field)
+        if Nx.dim() not in (2, 3) or Nx.shape != Ny.shape or (Nx.dim() == 3 and Nx.shape[0] != self.B):
+            raise ValueError(f"normal_field components of a ShapeLayer must be two [n1, n2] or [{self.B}, n1, n2] grids of one size, got "
+                             f"{list(Nx.shape)} and {list(Ny.shape)}")
+        n1, n2 = int(Nx.shape[-2]), int(Nx.shape[-1])
+        fits(n1, n2, 2, "the normal_field grid")         # the bound of trx_convmat_orders, as for a grid layer
+        Nx, Ny = Nx.expand(self.B, -1, -1), Ny.expand(self.B, -1, -1)
+        return torch.stack((Nx * Nx, Nx * Ny, Ny * Ny), dim=1).contiguous(), (n1, n2)
+
+    def _nv_tensor_shapes_torch(self, packed, rval, nn):
+        """(Exx, Exy, Eyy) of a ShapeLayer from the differentiable primitives: ShapeConvFn of the values and of the reciprocal values,
+        InverseFn, GemmFn; the field products nn are constants (the gradient is the derivative at a fixed field)."""
+        eng, cdt, B = self.engine, self._cdtype, self.B
+        conv_d = lambda val: ag.ShapeConvFn.apply(packed.par, val, packed, self._mn_dev, self._mmax, self._nmax, cdt, eng)
+        E = conv_d(packed.val)
+        D = E - ag.InverseFn.apply(conv_d(rval), eng)
+        C = eng.convmat_orders(nn.reshape(3 * B, *nn.shape[2:]), self._mn_dev, cdt, self._mmax, self._nmax).reshape(B, 3, E.shape[1], E.shape[2])
+        DC = [0.5 * (ag.GemmFn.apply(D, C[:, c].contiguous(), eng) + ag.GemmFn.apply(C[:, c].contiguous(), D, eng)) for c in range(3)]
+        return E - DC[0], -DC[1], E - DC[2]
 
     def _nv_tensor_torch(self, g, nn):
         """(Exx, Exy, Eyy) from the differentiable primitives: ConvMatFn of eps and 1/eps, InverseFn, GemmFn (the symmetrised products

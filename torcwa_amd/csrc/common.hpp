@@ -205,5 +205,15 @@ int convmat_orders_checked(hipStream_t s, int dtype, int cplx, const void* grid,
                            int nmax, void* out, void* ws);
 // the gather alone: out[b,i,j] = coef[b, m_i-m_j+2mmax, n_i-n_j+2nmax] from a finished complex128 box (list already checked)
 int orders_gather(hipStream_t s, int dtype, const cx<double>* coef, const int* mn, int N, int mmax, int nmax, int batch, void* out);
+// vector shapes (shapes.hip): the host check of kind / voff (one copy and one synchronisation of s) and the coefficient box
+// [batch, 4mmax+1, 4nmax+1] of a checked list (arguments as trx_convmat_shapes, validated by the caller)
+int shapes_list_check(hipStream_t s, const int* kind, const int* voff, int S, int npar);
+int shapes_coef_box(hipStream_t s, const int* kind, const int* voff, int S, const double* par, int npar, const void* val, const double* recip,
+                    double cell_area, int batch, int mmax, int nmax, cx<double>* box);
+// the tail of the normal-vector tensor (convmat_nv.hip), all complex128 [batch,N,N]: on entry oxx = [eps], R = [1/eps], C[b*3 + c] = [Nx^2],
+// [Nx Ny], [Ny^2]; on return oxx, oxy, oyy hold the tensor (R holds D) and, for dtype complex64, Exx / Exy / Eyy their rounded copies
+// (for complex128 the caller passes oxx = Exx, ...).  info[b] becomes 2 where it was 0 and [1/eps] is singular.
+int nv_tensor_tail(hipStream_t s, int dtype, int batch, int N, cx<double>* oxx, cx<double>* oxy, cx<double>* oyy, void* Exx, void* Exy, void* Eyy,
+                   int* info, cx<double>* R, cx<double>* C, void* inv_ws, size_t inv_bytes, int* piv, int* iinfo);
 
 }  // namespace trx

@@ -269,8 +269,18 @@ int convmat_nv_t(int cplx, const void* grid, int batch, int nx, int ny, int ox, 
     if ((rc = conv(1, gz, batch, oxx))) return rc;
     if ((rc = conv(1, rz, batch, R))) return rc;
     if ((rc = conv(0, nn, 3 * batch, C))) return rc;
+    return nv_tensor_tail(s, dtype, batch, N, oxx, oxy, oyy, Exx, Exy, Eyy, info, R, C, ws + L.inv, L.inv_bytes, piv, iinfo);
+}
+
+}  // namespace
+
+// the tail every normal-vector entry shares (the grid entries above, trx_convmat_nv_shapes): [1/eps]^-1, D, the six GEMMs, the store
+int nv_tensor_tail(hipStream_t s, int dtype, int batch, int N, zc* oxx, zc* oxy, zc* oyy, void* Exx, void* Exy, void* Eyy, int* info, zc* R, zc* C,
+                   void* inv_ws, size_t inv_bytes, int* piv, int* iinfo) {
+    const long NN = (long)N * N, bNN = (long)batch * NN;
+    int rc;
     if (hipMemcpyAsync(oyy, oxx, sizeof(zc) * (size_t)bNN, hipMemcpyDeviceToDevice, s) != hipSuccess) return TRX_ERR_LAUNCH;
-    if ((rc = trx_inverse(TRX_C128, R, N, batch, piv, iinfo, ws + L.inv, L.inv_bytes, s))) return rc;
+    if ((rc = trx_inverse(TRX_C128, R, N, batch, piv, iinfo, inv_ws, inv_bytes, s))) return rc;
     TRX_LAUNCH(nv_info_kernel, dim3(cdiv_i(batch, 256)), dim3(256), 0, s, (const int*)iinfo, batch, info);
     TRX_LAUNCH(nv_delta_kernel, dim3(cdiv_i(bNN, 256)), dim3(256), 0, s, (const zc*)oxx, R, bNN);
     TRX_CHECK_LAUNCH();
@@ -292,7 +302,6 @@ int convmat_nv_t(int cplx, const void* grid, int batch, int nx, int ny, int ox, 
     return TRX_OK;
 }
 
-}  // namespace
 }  // namespace trx
 
 using namespace trx;

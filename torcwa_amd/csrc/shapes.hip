@@ -363,6 +363,20 @@ inline bool good_area(double a) { return a > 0.0 && std::isfinite(a); }
 inline size_t box_bytes(int batch, int mmax, int nmax) { return sizeof(zc) * (size_t)batch * (4 * mmax + 1) * (4 * nmax + 1); }
 
 }  // namespace
+
+// the coefficient box alone (arguments validated by the caller): the one launch of shapes_coef_kernel, shared with trx_convmat_nv_shapes
+int shapes_coef_box(hipStream_t s, const int* kind, const int* voff, int S, const double* par, int npar, const void* val, const double* recip,
+                    double cell_area, int batch, int mmax, int nmax, cx<double>* box) {
+    const int nbox = (4 * mmax + 1) * (4 * nmax + 1);
+    const Recip r{recip[0], recip[1], recip[2], recip[3]};
+    TRX_LAUNCH(shapes_coef_kernel, dim3(cdiv_i(nbox, SH_BLOCK), batch), dim3(SH_BLOCK), sizeof(double) * (SH_BLOCK + 2), s, kind, voff, S, par,
+               npar, (const zc*)val, r, 1.0 / cell_area, mmax, nmax, box);
+    TRX_CHECK_LAUNCH();
+    return TRX_OK;
+}
+
+int shapes_list_check(hipStream_t s, const int* kind, const int* voff, int S, int npar) { return shapes_check(s, kind, voff, S, npar); }
+
 }  // namespace trx
 
 extern "C" size_t trx_convmat_shapes_ws_bytes(int dtype, int batch, int N, int mmax, int nmax) {
@@ -387,11 +401,8 @@ extern "C" int trx_convmat_shapes(int dtype, const int* kind, const int* voff, i
     rc = shapes_check(s, kind, voff, S, npar);
     if (rc) return rc;
     zc* box = reinterpret_cast<zc*>(coef ? coef : ws);
-    const int nbox = (4 * mmax + 1) * (4 * nmax + 1);
-    const Recip r{recip[0], recip[1], recip[2], recip[3]};
-    TRX_LAUNCH(shapes_coef_kernel, dim3(cdiv_i(nbox, SH_BLOCK), batch), dim3(SH_BLOCK), sizeof(double) * (SH_BLOCK + 2), s, kind, voff, S, par,
-               npar, (const zc*)val, r, 1.0 / cell_area, mmax, nmax, box);
-    TRX_CHECK_LAUNCH();
+    rc = shapes_coef_box(s, kind, voff, S, par, npar, val, recip, cell_area, batch, mmax, nmax, box);
+    if (rc) return rc;
     return orders_gather(s, dtype, box, mn, N, mmax, nmax, batch, out);
 }
 

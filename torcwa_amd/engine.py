@@ -322,6 +322,46 @@ class Engine:
         self._info(info, "convmat_nv_orders (1: zero grid value, 2: singular [1/eps])")
         return Exx, Exy, Eyy
 
+    @_phase("assembly (convolution matrices, E^-1, A = PQ)")
+    def shape_normal_field(self, packed, lattice, n1, n2):
+        """Packed vector shapes and the lattice (rows a1, a2) -> [B,3,n1,n2] float64 products (Nx^2, Nx Ny, Ny^2) of the blended normal field
+        of the shape list at the DFT's sample positions (include/trx.h: trx_shape_normal_field)."""
+        kind, voff, par, _, _ = self._shape_args(packed)
+        B, npar = par.shape
+        nn = torch.empty((B, 3, int(n1), int(n2)), dtype=torch.float64, device=self.device)
+        self.lib.check(self.lib.shape_normal_field(kind.data_ptr(), voff.data_ptr(), int(kind.numel()), par.data_ptr(), npar, self._cell(lattice),
+                                                   B, int(n1), int(n2), nn.data_ptr(), self.stream))
+        return nn
+
+    @_phase("assembly (convolution matrices, E^-1, A = PQ)")
+    def convmat_nv_shapes(self, packed, rval, lattice, mn, dtype, n1, n2, *, nn=None, mmax=None, nmax=None):
+        """Packed vector shapes -> (Exx, Exy, Eyy) [B,N,N], the normal-vector tensor with closed-form [eps] and [1/eps] (include/trx.h:
+        trx_convmat_nv_shapes).  rval: [B,S+1] reciprocal values (shapes.ShapeLayer.reciprocal_values); nn: [B,3,n1,n2] float64 products of a
+        supplied field, or None to sample the field of the shape list on n1 x n2."""
+        kind, voff, par, val, recip = self._shape_args(packed)
+        B, npar = par.shape
+        n1, n2 = int(n1), int(n2)
+        rval = self._c(rval.detach().to(device=self.device, dtype=torch.complex128))
+        if tuple(rval.shape) != tuple(val.shape):
+            raise ValueError(f"reciprocal values must be {list(val.shape)} like val, got {list(rval.shape)}")
+        mn, N, mmax, nmax = self._orders(mn, mmax, nmax)
+        Exx = torch.empty((B, N, N), dtype=dtype, device=self.device)
+        Exy, Eyy = torch.empty_like(Exx), torch.empty_like(Exx)
+        if nn is not None:
+            nn = self._c(nn.to(device=self.device, dtype=torch.float64))
+            if tuple(nn.shape) != (B, 3, n1, n2):
+                raise ValueError(f"normal-field products must be [{B}, 3, {n1}, {n2}], got {list(nn.shape)}")
+        info = self._ints(B)
+        nws = self.lib.convmat_nv_shapes_ws_bytes(_CODE[dtype], B, n1, n2, N, mmax, nmax)
+        ws = self._ws(nws)
+        self.lib.check(self.lib.convmat_nv_shapes(_CODE[dtype], kind.data_ptr(), voff.data_ptr(), int(kind.numel()), par.data_ptr(), npar,
+                                                  val.data_ptr(), rval.data_ptr(), ctypes.addressof(recip), float(packed.cell_area),
+                                                  self._cell(lattice), B, n1, n2, mn.data_ptr(), N, mmax, nmax,
+                                                  nn.data_ptr() if nn is not None else None, Exx.data_ptr(), Exy.data_ptr(), Eyy.data_ptr(),
+                                                  info.data_ptr(), ws.data_ptr(), nws, self.stream))
+        self._info(info, "convmat_nv_shapes (1: a medium with eps zero or non-finite, 2: singular [1/eps])")
+        return Exx, Exy, Eyy
+
     # -- dense blocks ----------------------------------------------------------------------------------
     def gemm(self, A, Bm, *, opA=0, opB=0, alpha=1.0, beta=0.0, out=None):
         """Batched C = alpha op(A) op(B) + beta C for contiguous [B,*,*] operands."""

@@ -13,6 +13,14 @@ _LI_EXTRA = 0.5
 # fourier_rule="normal": Exx, Exy, Eyy (three N x N) next to E, E^-1 while A is built, and inside trx_convmat_nv the workspace ([1/eps], its
 # inverse's workspace and the three product matrices: five more N x N) -- 8 N^2 = 2 n^2
 _NV_EXTRA = 2.0
+# fourier_rule="normal" on a ShapeLayer (trx_convmat_nv_shapes): the tensor and the workspace matrices are those of _NV_EXTRA; on top, per point,
+# the three fp64 products of the field on the shape_nv_grid (24 n1 n2 bytes), the row transforms of their pruned DFT (3 x 16 n1 (4 nmax + 1))
+# and the coefficient boxes (4 x 16 (4 mmax + 1)(4 nmax + 1)).  From the workspace layout; not measured on the allocator yet.
+def _shape_nv_bytes(shape_nv_grid, mmax, nmax):
+    n1, n2 = (shape_nv_grid, shape_nv_grid) if isinstance(shape_nv_grid, int) else shape_nv_grid
+    return 24 * n1 * n2 + 48 * n1 * (4 * nmax + 1) + 64 * (4 * mmax + 1) * (4 * nmax + 1)
+
+
 _HEADROOM = 0.10                               # fraction of the device memory a sweep leaves free
 # Thickness sweep (add_layer(..., swept=True)), matrices per (point, thickness) that one trx_thickness_columns call holds, from its workspace
 # layout (include/trx.h): X rho X and K, 2 n x n; the amplitudes and the pivots are O(n m) and O(n) next to them.  They come on top of what stays
@@ -32,7 +40,8 @@ _THICKNESS_MATRICES = 2.0
 _ABS_EXTRA_PER_LAYER = 15.0
 
 
-def auto_chunk(B, order, n_layers, precision, device, dtype=torch.complex64, streams=1, fourier_rule="laurent", absorption=False):
+def auto_chunk(B, order, n_layers, precision, device, dtype=torch.complex64, streams=1, fourier_rule="laurent", absorption=False,
+               shape_nv_grid=None):
     """Largest number of points solved in lock-step that fits the free HBM of `device` with _HEADROOM to spare (a multiple of 8 when it
     is cut: the mixed-precision eigensolver and its iteration groups want batches of at least 8).  Raises with the numbers when not even
     one point fits -- instead of an allocator error in the middle of a solve."""
@@ -47,6 +56,9 @@ def auto_chunk(B, order, n_layers, precision, device, dtype=torch.complex64, str
     if absorption:
         mats += _ABS_EXTRA_PER_LAYER * max(1, int(n_layers))
     per_point = mats * n * n * elem * max(1, int(streams))
+    if fourier_rule == "normal" and shape_nv_grid is not None:      # a ShapeLayer in the stack: its field products and their transforms
+        mmax, nmax = (box[0], box[1]) if kind == "rect" else (int(abs(mn[:, 0]).max()), int(abs(mn[:, 1]).max()))
+        per_point += _shape_nv_bytes(shape_nv_grid, mmax, nmax) * max(1, int(streams))
     free, total = torch.cuda.mem_get_info(device)
     free += torch.cuda.memory_reserved(device) - torch.cuda.memory_allocated(device)      # the caching allocator's idle blocks are ours to reuse
     budget = free - _HEADROOM * total

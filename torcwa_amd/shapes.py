@@ -180,6 +180,13 @@ class ShapeLayer:
                       torch.tensor(voff, dtype=torch.int32, device=device), torch.cat(rows, dim=1), val,
                       tuple(float(v) for v in recip.ravel()), float(area))
 
+    def reciprocal_values(self, B, device):
+        """[B, S+1] complex128, the `rval` of trx_convmat_nv_shapes: 1/eps of the background, then 1/eps_s - 1/eps_host per shape -- the
+        `val` of pack() for the reciprocal permittivity.  Stays in the autograd graph."""
+        bvec = lambda t: t.to(device).expand(B)
+        rbg = 1 / bvec(self.background)
+        return torch.stack([rbg] + [1 / bvec(s.eps) - (rbg if s.host is None else 1 / bvec(s.host.eps)) for s in self.shapes], dim=1)
+
     def rasterise(self, a1, a2, n1, n2, device=None):
         """Hard-edged [B, n1, n2] eps grid sampled at (x / n1) a1 + (y / n2) a2 -- the DFT's positions, not the half-pixel-shifted ones of
         `geometry`.  Shapes that cross the cell boundary wrap around (the eight neighbouring images are tested).  For comparisons with the grid
@@ -198,3 +205,23 @@ class ShapeLayer:
                     inside |= s._inside(X - i * a1[0] - j * a2[0], Y - i * a1[1] - j * a2[1], B)
             grid = torch.where(inside, bvec(s.eps)[:, None, None], grid)
         return grid
+
+
+def nv_grid(shape_nv_grid):
+    """(n1, n2) of the `shape_nv_grid` keyword: an int or a pair of ints, each in 1 .. 2048."""
+    g = (shape_nv_grid, shape_nv_grid) if isinstance(shape_nv_grid, (int, np.integer)) else tuple(shape_nv_grid)
+    if len(g) != 2 or not all(isinstance(v, (int, np.integer)) and 1 <= v <= 2048 for v in g):
+        raise ValueError(f"shape_nv_grid must be an int or (n1, n2) with 1 <= n <= 2048, got {shape_nv_grid!r}")
+    return int(g[0]), int(g[1])
+
+
+def normal_products(layer, lattice, n1, n2, B=None, engine=None):
+    """[B, 3, n1, n2] float64 products (Nx^2, Nx Ny, Ny^2) of the blended normal field of a ShapeLayer (include/trx.h:
+    trx_shape_normal_field), sampled at (i / n1) a1 + (j / n2) a2 like `rasterise`: what fourier_rule="normal" derives for the layer.  For
+    inspection, and for experiments with add_layer(normal_field=...).  lattice: [Lx, Ly] or the 2 x 2 rows a1, a2."""
+    from . import lattice as _lat
+    from .engine import default_engine
+    eng = engine if engine is not None else default_engine()
+    A = _lat.lattice_matrix(lattice)
+    B = layer.batch if B is None else int(B)
+    return eng.shape_normal_field(layer.pack(A, B, eng.device), A, n1, n2)

@@ -80,12 +80,12 @@ def rectangle_density(nx, ny, Lx, Ly, Wx, Wy, Cx, Cy, theta=0.0, edge_sharpness=
 
 
 def _solve_chunk(freq, layers, order, L, eps_in, eps_out, inc_ang, azi_ang, dtype, precision, engine, orders,
-                 polarization, direction, port, eig_route="auto", route_hint=None, fourier_rule="laurent", nv_sigma=NV_SIGMA_DEFAULT,
+                 polarization, direction, port, eig_route="auto", route_hint=None, fourier_rule="laurent", nv_sigma=NV_SIGMA_DEFAULT, shape_nv_grid=None,
                  absorption=False, source=None, symmetry=None, symmetry_tol=1e-6, symmetry_sector=False):
     """layers: list of (thickness, eps[, mu]); thickness scalar or [b]; eps/mu scalar, [b] or [b,nx,ny].  absorption: the chunk keeps W, V and
     the coupling matrices (keep_coupling=True, no streaming cascade) and returns (S-parameters, BatchedRCWA.absorption())."""
     sim = BatchedRCWA(freq, order, L, dtype=dtype, precision=precision, engine=engine, keep_coupling=bool(absorption), fold_layers=not absorption,
-                      eig_route=eig_route, route_hint=route_hint, fourier_rule=fourier_rule, nv_sigma=nv_sigma,
+                      eig_route=eig_route, route_hint=route_hint, fourier_rule=fourier_rule, nv_sigma=nv_sigma, shape_nv_grid=shape_nv_grid,
                       symmetry=symmetry, symmetry_tol=symmetry_tol, symmetry_sector=symmetry_sector)
     if eps_in is not None:
         sim.add_input_layer(eps=eps_in)
@@ -118,6 +118,11 @@ def _slice(v, lo, hi, B):
     return v
 
 
+def _shape_grid_of(layers, shape_nv_grid):
+    """shape_nv_grid for the memory model when a layer of the stack is a ShapeLayer (its field products are sampled per point), else None."""
+    return shape_nv_grid if any(isinstance(v, ShapeLayer) for lay in layers for v in lay) else None
+
+
 def _source_amplitudes(source, B):
     """(M, per_point) of a sweep's source keywords: M orders, and whether `amplitude` carries a leading B.  Anything else is refused here,
     before any chunk is solved."""
@@ -135,7 +140,7 @@ def _source_amplitudes(source, B):
 def solve_stack_sweep(freq, layers, order, L, *, eps_in=None, eps_out=None, inc_ang=0.0, azi_ang=0.0, dtype=torch.complex64,
                       precision="high", engine=None, chunk=None, streams=1, orders=((0, 0),), polarization="xx",
                       direction="forward", port="transmission", check_info=True, eig_route="auto", fourier_rule="laurent",
-                      nv_sigma=NV_SIGMA_DEFAULT, absorption=False, source=None, symmetry=None, symmetry_tol=1e-6, symmetry_sector=False):
+                      nv_sigma=NV_SIGMA_DEFAULT, shape_nv_grid=None, absorption=False, source=None, symmetry=None, symmetry_tol=1e-6, symmetry_sector=False):
     """B sweep points of a multi-layer stack (BASELINE.json configs 2-4): the reference's per-point Python loop
     (example/Example1-1.ipynb, Example3.ipynb) as chunks of a batched solve.  `layers` as in `_solve_chunk`, with
     per-point quantities carrying a leading dimension B = len(freq).  Returns the requested S-parameter [B, len(orders)].
@@ -144,7 +149,8 @@ def solve_stack_sweep(freq, layers, order, L, *, eps_in=None, eps_out=None, inc_
     of this call use the all-fp64 route -- BatchedRCWA._eig_call), "mixed" or "fp64".
 
     fourier_rule: "laurent" (default), "li" (Li's inverse rule in every patterned layer, BatchedRCWA) or "normal" (the normal-vector method,
-    the field derived from each grid with a Gaussian of nv_sigma cells).
+    the field derived from each grid with a Gaussian of nv_sigma cells; for a ShapeLayer the blended field of the shape list sampled on
+    shape_nv_grid, an int or (n1, n2)).
 
     symmetry: None | "x" | "y" | "xy" -- mirror planes of every patterned layer (kx0 = 0 / ky0 = 0 at every point); each layer eigenproblem is
     folded into 2 / 4 independent blocks (BatchedRCWA, torcwa_amd/symmetry.py).  ValueError from the first chunk if a grid, the order set, the
@@ -175,12 +181,13 @@ def solve_stack_sweep(freq, layers, order, L, *, eps_in=None, eps_out=None, inc_
             src = dict(source, amplitude=torch.as_tensor(source["amplitude"]).reshape(B, n_src, 2)[lo:hi])
         return _solve_chunk(freq[lo:hi], lays, order, L, _slice(eps_in, lo, hi, B), _slice(eps_out, lo, hi, B), _slice(inc_ang, lo, hi, B),
                             _slice(azi_ang, lo, hi, B), dtype, precision, engine, orders, polarization, direction, port,
-                            eig_route=eig_route, route_hint=route_hint, fourier_rule=fourier_rule, nv_sigma=nv_sigma, absorption=absorption,
+                            eig_route=eig_route, route_hint=route_hint, fourier_rule=fourier_rule, nv_sigma=nv_sigma, shape_nv_grid=shape_nv_grid, absorption=absorption,
                             source=src if absorption else None, symmetry=symmetry, symmetry_tol=symmetry_tol, symmetry_sector=symmetry_sector)
 
     # chunk=None: as many points in lock-step as the free HBM holds (the reference's per-point loop cannot run out of memory; neither must this)
     outs = _solve_chunks(solve, B, freq.device, engine, check_info, streams, chunk or (lambda: auto_chunk(
-        B, order, len(layers), precision, freq.device, dtype=dtype, streams=streams, fourier_rule=fourier_rule, absorption=absorption)))
+        B, order, len(layers), precision, freq.device, dtype=dtype, streams=streams, fourier_rule=fourier_rule, absorption=absorption,
+        shape_nv_grid=_shape_grid_of(layers, shape_nv_grid))))
     if absorption:
         return (torch.cat([o[0] for o in outs], dim=0), {k: torch.cat([o[1][k] for o in outs], dim=0) for k in outs[0][1]})
     return torch.cat(outs, dim=0)
@@ -260,7 +267,7 @@ def solve_single_layer_sweep(freq, eps_grids, thickness, order, L, **kw):
 def solve_thickness_sweep(freq, layers, order, L, *, layer=0, thicknesses, eps_in=None, eps_out=None, inc_ang=0.0, azi_ang=0.0,
                           dtype=torch.complex64, precision="high", engine=None, chunk=None, streams=1, orders=((0, 0),), polarization="xx",
                           direction="forward", port="transmission", check_info=True, eig_route="auto", fourier_rule="laurent",
-                          nv_sigma=NV_SIGMA_DEFAULT, symmetry=None, symmetry_tol=1e-6, thickness_chunk=None):
+                          nv_sigma=NV_SIGMA_DEFAULT, shape_nv_grid=None, symmetry=None, symmetry_tol=1e-6, thickness_chunk=None):
     """B sweep points x T thicknesses of ONE layer of a stack: the modes of `layers[layer]` are computed once per point and every thickness
     costs one GEMM and one LU (BatchedRCWA.add_layer(..., swept=True)) instead of a new eigendecomposition.  Returns [B, T, len(orders)].
 
@@ -283,7 +290,7 @@ def solve_thickness_sweep(freq, layers, order, L, *, layer=0, thicknesses, eps_i
 
     def solve(lo, hi, route_hint):
         sim = BatchedRCWA(freq[lo:hi], order, L, dtype=dtype, precision=precision, engine=engine, keep_coupling=False, fold_layers=True,
-                          eig_route=eig_route, route_hint=route_hint, fourier_rule=fourier_rule, nv_sigma=nv_sigma, symmetry=symmetry,
+                          eig_route=eig_route, route_hint=route_hint, fourier_rule=fourier_rule, nv_sigma=nv_sigma, shape_nv_grid=shape_nv_grid, symmetry=symmetry,
                           symmetry_tol=symmetry_tol)
         sim.thickness_chunk = thickness_chunk
         if eps_in is not None:
@@ -300,4 +307,5 @@ def solve_thickness_sweep(freq, layers, order, L, *, layer=0, thicknesses, eps_i
         return sim.solve_S_parameters([list(o) for o in orders], direction=direction, port=port, polarization=polarization)
 
     return torch.cat(_solve_chunks(solve, B, freq.device, engine, check_info, streams, chunk or (lambda: auto_chunk(
-        B, order, len(layers), precision, freq.device, dtype=dtype, streams=streams, fourier_rule=fourier_rule))), dim=0)
+        B, order, len(layers), precision, freq.device, dtype=dtype, streams=streams, fourier_rule=fourier_rule,
+        shape_nv_grid=_shape_grid_of(layers, shape_nv_grid)))), dim=0)
