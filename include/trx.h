@@ -181,9 +181,37 @@ int trx_convmat_shapes_backward(const int* kind, const int* voff, int S, const d
  * background entry is zero (a medium with eps zero or non-finite); 2 [1/eps] is singular.  An all-zero nn returns Exx = Eyy = the out of
  * trx_convmat_shapes bit for bit and Exy = 0.  Requires n1 > 2 mmax, n2 > 2 nmax (the bound of trx_convmat_orders; the box of the products
  * reaches +-2 mmax, so a grid with n1 <= 4 mmax aliases its outer coefficients -- the Python layer asks for n1 > 4 mmax), n1, n2 <= 2048
- * (TRX_ERR_UNSUPPORTED) and 3 batch <= 65535 (TRX_ERR_ARG).  All arithmetic is fp64 for both dtypes. */
+ * (TRX_ERR_UNSUPPORTED) and 3 batch <= 65535 (TRX_ERR_ARG).  All arithmetic is fp64 for both dtypes.
+ *
+ * trx_shape_normal_field_backward: the adjoint of trx_shape_normal_field, gpar[b,k] = sum_{c,i,j} gnn[b,c,i,j] d nn[b,c,i,j] / d par[b,k]
+ * (gnn [batch,3,n1,n2] fp64, gpar [batch,npar] fp64, every element written), with the forward's primitives, nine images, eta^2 and coherence
+ * floor.  The forward is piecewise smooth and the derivative is that of the current piece.  Branch conventions (part of the contract):
+ *   - a sample whose forward products are 0 contributes nothing (coherence <= 1e-3; |g| = 0; a vertex hit with delta = 0 adds no term);
+ *   - the derivative of |.| at 0 is 0 (it is multiplied by delta in dw/ddelta = -4 delta w / (delta^2 + eta^2) anyway);
+ *   - the derivative of min(Rx, Ry) goes to Rx when Rx <= Ry, else to Ry (a circle, whose R is packed into both, gets the right total);
+ *   - on the vertex branch of an edge (tau < 0 or tau > 1) the derivative goes to the vertex that was selected; a sample on a branch line
+ *     (tau = 0 or 1 -- round coordinates on a regular grid do hit them) sits on a C0 kink of the field and takes the mean of the two pieces'
+ *     derivatives: the symmetric derivative, what a central difference sees, as sign(0) = 0 is for |.|.  On the line means to within rounding:
+ *     |(r' - a).e - t| <= 16 eps (|(r' - a)_x e_x| + |(r' - a)_y e_y| + t) for t = 0 or |e|^2, about 1e-14 of the cell in distance;
+ *   - a rectangle's (Wx, Wy, Cx, Cy, theta) receive the chain rule through its four vertices; a slot of the row no shape owns receives 0.
+ * Per sample J is recomputed as the forward does, in the same order, and the direction step is differentiated in the scaled form
+ * k = (a o/r - beta d/r) / r, a = (g_xx - g_yy)/2, beta = g_xy/2: g_d = (o/r) k on d(Jxx - Jyy), g_o = -(d/r) k on d(2 Jxy) -- the unit vector and a
+ * single 1/r.  G = [[g_d, g_o], [g_o, -g_d]] is trace-free and orthogonal to J; each term w n n^T, w = 1/(delta^2 + eta^2)^2, contributes
+ * dw (n^T G n) + 2 w (t^T G n)(t . dn), t = (-n_y, n_x), formed from the term's own unit normal.  Three launches, no atomics: (1) the forward's
+ * kernel with the direction adjoint as its epilogue writes G [batch,2,n1,n2]; (2) grid (chunk, slot, batch), 256 threads: a workgroup is live
+ * on the first slot of an ellipse / rectangle and on the x slot of a polygon vertex (the edge that starts there); it accumulates the <= 5
+ * partials of that primitive over its chunk of samples x 9 images in registers (samples with G = 0 are skipped) and reduces them by the
+ * fixed wave_sum tree and an ascending sum over its four waves; chunks: min(ceil(n1 n2 / 256), 256), so one disk at 256 x 256 is 256
+ * workgroups; (3) one thread per (b, slot) sums the chunks in ascending order, for a polygon vertex the edge that ends there and then the edge
+ * that starts there.  Bit-identical on repetition.  Work model: the forward again plus one derivative pass of the same 9 (ellipses + edges)
+ * evaluations per sample (about three times the divides of the forward's); traffic 24 + 2 x 16 B per sample.  TRX_ERR_ARG as the forward
+ * entry (and for gnn, gpar or ws NULL), TRX_ERR_WORKSPACE below trx_shape_normal_field_backward_ws_bytes, TRX_ERR_UNSUPPORTED for n1 or
+ * n2 > 2048 or npar > 65535; a refused call writes nothing. */
 int trx_shape_normal_field(const int* kind, const int* voff, int S, const double* par, int npar, const double* lattice, int batch, int n1, int n2,
                            double* nn, void* stream);
+size_t trx_shape_normal_field_backward_ws_bytes(int S, int npar, int batch, int n1, int n2);
+int trx_shape_normal_field_backward(const int* kind, const int* voff, int S, const double* par, int npar, const double* lattice, int batch, int n1,
+                                    int n2, const double* gnn, double* gpar, void* ws, size_t ws_bytes, void* stream);
 size_t trx_convmat_nv_shapes_ws_bytes(int dtype, int batch, int n1, int n2, int N, int mmax, int nmax);
 int trx_convmat_nv_shapes(int dtype, const int* kind, const int* voff, int S, const double* par, int npar, const void* val, const void* rval,
                           const double* recip, double cell_area, const double* lattice, int batch, int n1, int n2, const int* mn, int N, int mmax,

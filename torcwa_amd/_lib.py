@@ -47,6 +47,9 @@ _SIGS = {
     "trx_convmat_shapes_backward": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_double, c_int, c_int, c_int,
                                             c_void_p, c_void_p, c_void_p, c_void_p]),
     "trx_shape_normal_field": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
+    "trx_shape_normal_field_backward_ws_bytes": (c_size_t, [c_int, c_int, c_int, c_int, c_int]),
+    "trx_shape_normal_field_backward": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p,
+                                                c_void_p, c_size_t, c_void_p]),
     "trx_convmat_nv_shapes_ws_bytes": (c_size_t, [c_int, c_int, c_int, c_int, c_int, c_int, c_int]),
     "trx_convmat_nv_shapes": (c_int, [c_int, c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_double, c_void_p, c_int,
                                       c_int, c_int, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,

@@ -108,6 +108,44 @@ def _twiddle(n, o, dev):
     return torch.exp(2j * math.pi * ((r * q) % n).to(torch.float64) / n)
 
 
+class ShapeNormalFieldFn(torch.autograd.Function):
+    """nn = shape_normal_field(par) (include/trx.h: trx_shape_normal_field), the [B,3,n1,n2] products of the blended normal field of a packed
+    shape list, differentiable in the parameter rows par [B, npar]: the backward is trx_shape_normal_field_backward, the derivative of the
+    piece of the (piecewise smooth) forward the parameters lie on, bit-reproducible.  Once differentiable."""
+
+    @staticmethod
+    def forward(ctx, par, packed, lattice, n1, n2, engine):
+        packed = packed._replace(par=par.detach())
+        ctx.meta = (packed, lattice, engine, par.dtype)
+        return engine.shape_normal_field(packed, lattice, n1, n2)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, gnn):
+        packed, lattice, engine, pdt = ctx.meta
+        return engine.shape_normal_field_backward(packed, lattice, gnn).to(pdt), None, None, None, None, None
+
+
+class FieldConvFn(torch.autograd.Function):
+    """C = convmat_orders(g, mn) of REAL grids g [B,n1,n2] (the products of a normal field), differentiable in g.  The backward is the adjoint of
+    the gather by trx_toeplitz_sums (fixed-order sums: ConvMatOrdersFn's index_add_ is an atomic scatter on the GPU and would cost the path its
+    bit-reproducibility), then the conjugate pruned DFT over the coefficient box as two small twiddle products, real part.  Once differentiable."""
+
+    @staticmethod
+    def forward(ctx, grid, mn, mmax, nmax, cdtype, engine):
+        ctx.meta = (mn, mmax, nmax, engine, tuple(grid.shape), grid.dtype)
+        return engine.convmat_orders(grid, mn, cdtype, mmax, nmax)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, gC):
+        mn, mmax, nmax, engine, (B, n1, n2), gdt = ctx.meta
+        G = engine.toeplitz_sums(gC, mn, mmax, nmax)                          # [B, 4mmax+1, 4nmax+1] complex128
+        Fx, Fy = _twiddle(n1, mmax, gC.device), _twiddle(n2, nmax, gC.device)
+        g = torch.real(Fx[None] @ G @ Fy.transpose(0, 1)[None]) / (n1 * n2)   # [B, n1, n2]
+        return g.to(gdt), None, None, None, None, None
+
+
 def _diag_index(w, o, dev):
     """Flattened (a, a') of a w x w block -> a - a' + 2o (w = 2o+1): the Toeplitz diagonal of each entry."""
     a = torch.arange(w, device=dev)

@@ -79,7 +79,7 @@ class BatchedRCWA(FluxMixin, BatchedFieldMixin, VolumeMixin, ReadoutMixin, Secto
                  avoid_Pinv_instability=False, max_Pinv_instability=0.005, precision="high", engine=None,
                  keep_coupling=True, fold_layers=False, eig_route="auto", route_hint=None, fourier_rule="laurent", nv_sigma=NV_SIGMA_DEFAULT,
                  symmetry=None, symmetry_tol=1e-6, symmetry_grad=False, symmetry_sector=False, sector_grad=False, swept_grad=False,
-                 shape_nv_grid=None):
+                 shape_nv_grid=None, shape_nv_grad=False):
         check_fourier_rule(fourier_rule)
         # symmetry (extension): None | "x" | "y" | "xy" -- the caller states that every patterned layer is invariant under x -> -x (y -> -y) about
         # a plane and that kx0 = 0 (ky0 = 0) at every sweep point.  A = P Q of such a layer is then folded into 2 / 4 independent eigenproblems
@@ -132,6 +132,13 @@ class BatchedRCWA(FluxMixin, BatchedFieldMixin, VolumeMixin, ReadoutMixin, Secto
         # (trx_convmat_nv_shapes) unless add_layer(normal_field=...) supplies one on a grid of its own
         # None (the default): a ShapeLayer without a supplied field stays refused under this rule, as before the rule reached shapes
         self.shape_nv_grid = None if shape_nv_grid is None else _shapes.nv_grid(shape_nv_grid)
+        # shape_nv_grad=True (opt-in): the field a ShapeLayer derives on shape_nv_grid stays in the autograd graph (ShapeNormalFieldFn ->
+        # FieldConvFn), so the gradient with respect to the geometry is the derivative of the forward, the dependence of the blend on the
+        # parameters included -- wherever the piecewise smooth forward is differentiable.  False: the derived field is a constant of the
+        # graph, as before, bit for bit.  A field supplied with add_layer(normal_field=...) is a constant whatever this keyword says.
+        self.shape_nv_grad = bool(shape_nv_grad)
+        if self.shape_nv_grad and fourier_rule != "normal":
+            raise ValueError(f'shape_nv_grad=True needs fourier_rule="normal", got {fourier_rule!r}: only that rule derives a normal field')
         if dtype != torch.complex64 and dtype != torch.complex128:                      # rcwa.py:37-41
             warnings.warn("Invalid simulation data type. Set as torch.complex64.", UserWarning)
             dtype = torch.complex64
@@ -317,7 +324,9 @@ class BatchedRCWA(FluxMixin, BatchedFieldMixin, VolumeMixin, ReadoutMixin, Secto
         autograd.  None: the field is derived from the eps grid (trx_normal_field, nv_sigma).  With eps a ShapeLayer the grids may have any
         size n1 > 2 mmax, n2 > 2 nmax (at most 2048), sampled at (i / n1) a1 + (j / n2) a2 like ShapeLayer.rasterise; None: the blended field
         of the shape list on shape_nv_grid (trx_shape_normal_field); one tensor [3, n1, n2] or [B, 3, n1, n2] is taken as the
-        products (Nx^2, Nx Ny, Ny^2) themselves, as shapes.normal_products returns them.
+        products (Nx^2, Nx Ny, Ny^2) themselves, as shapes.normal_products returns them.  A supplied field is a constant of the graph; the
+        derived one is too unless the solver was built with shape_nv_grad=True (then gradients include the field's dependence on the
+        geometry, trx_shape_normal_field_backward).
         swept=True: `thickness` is a sweep axis, [T] (shared by the points) or [B, T].  The layer's modes are computed once, exactly as for a
         plain layer, and solve_S_parameters returns [B, T, len(orders)] (one GEMM and one LU per thickness, include/trx.h:
         trx_thickness_prepare / trx_thickness_columns).  At most one swept layer; needs keep_coupling=False, and a non-differentiable stack
@@ -480,7 +489,9 @@ class BatchedRCWA(FluxMixin, BatchedFieldMixin, VolumeMixin, ReadoutMixin, Secto
                 rval = v.reciprocal_values(self.B, self._device)
                 nn, (n1, n2) = self._shape_nv_products(normal_field)
                 if diff:
-                    if nn is None:             # the field derived from the shape list is a constant of the differentiable path (detached)
+                    if nn is None and self.shape_nv_grad:      # the derived field carries its dependence on the parameters
+                        nn = ag.ShapeNormalFieldFn.apply(packed.par, packed, self._lattice, n1, n2, eng)
+                    elif nn is None:           # the field derived from the shape list is a constant of the differentiable path (detached)
                         nn = eng.shape_normal_field(packed, self._lattice, n1, n2)
                     return self._nv_tensor_shapes_torch(packed, rval, nn)
                 return eng.convmat_nv_shapes(packed, rval, self._lattice, self._mn_dev, cdt, n1, n2, nn=nn, mmax=self._mmax, nmax=self._nmax)
@@ -645,12 +656,17 @@ class BatchedRCWA(FluxMixin, BatchedFieldMixin, VolumeMixin, ReadoutMixin, Secto
 
     def _nv_tensor_shapes_torch(self, packed, rval, nn):
         """(Exx, Exy, Eyy) of a ShapeLayer from the differentiable primitives: ShapeConvFn of the values and of the reciprocal values,
-        InverseFn, GemmFn; the field products nn are constants (the gradient is the derivative at a fixed field)."""
+        InverseFn, GemmFn.  Field products nn that carry no graph are constants (the gradient is the derivative at a fixed field, INTEGRATION.md
+        section A); those of ShapeNormalFieldFn (shape_nv_grad=True) pass their gradient on through FieldConvFn and GemmFn's second operand."""
         eng, cdt, B = self.engine, self._cdtype, self.B
         conv_d = lambda val: ag.ShapeConvFn.apply(packed.par, val, packed, self._mn_dev, self._mmax, self._nmax, cdt, eng)
         E = conv_d(packed.val)
         D = E - ag.InverseFn.apply(conv_d(rval), eng)
-        C = eng.convmat_orders(nn.reshape(3 * B, *nn.shape[2:]), self._mn_dev, cdt, self._mmax, self._nmax).reshape(B, 3, E.shape[1], E.shape[2])
+        if nn.requires_grad:
+            C = ag.FieldConvFn.apply(nn.reshape(3 * B, *nn.shape[2:]), self._mn_dev, self._mmax, self._nmax, cdt, eng)
+        else:
+            C = eng.convmat_orders(nn.reshape(3 * B, *nn.shape[2:]), self._mn_dev, cdt, self._mmax, self._nmax)
+        C = C.reshape(B, 3, E.shape[1], E.shape[2])
         DC = [0.5 * (ag.GemmFn.apply(D, C[:, c].contiguous(), eng) + ag.GemmFn.apply(C[:, c].contiguous(), D, eng)) for c in range(3)]
         return E - DC[0], -DC[1], E - DC[2]
 

@@ -334,6 +334,24 @@ class Engine:
         return nn
 
     @_phase("assembly (convolution matrices, E^-1, A = PQ)")
+    def shape_normal_field_backward(self, packed, lattice, gnn):
+        """gpar [B, npar] fp64 from the gradient gnn [B,3,n1,n2] of the field products: the adjoint of shape_normal_field (include/trx.h:
+        trx_shape_normal_field_backward)."""
+        kind, voff, par, _, _ = self._shape_args(packed)
+        B, npar = par.shape
+        gnn = self._c(gnn.to(device=self.device, dtype=torch.float64))
+        if gnn.dim() != 4 or tuple(gnn.shape[:2]) != (B, 3):
+            raise ValueError(f"the gradient of the field products must be [{B}, 3, n1, n2], got {list(gnn.shape)}")
+        n1, n2 = int(gnn.shape[2]), int(gnn.shape[3])
+        S = int(kind.numel())
+        gpar = torch.empty((B, npar), dtype=torch.float64, device=self.device)
+        nws = self.lib.shape_normal_field_backward_ws_bytes(S, npar, B, n1, n2)
+        ws = self._ws(nws)
+        self.lib.check(self.lib.shape_normal_field_backward(kind.data_ptr(), voff.data_ptr(), S, par.data_ptr(), npar, self._cell(lattice), B, n1,
+                                                            n2, gnn.data_ptr(), gpar.data_ptr(), ws.data_ptr(), nws, self.stream))
+        return gpar
+
+    @_phase("assembly (convolution matrices, E^-1, A = PQ)")
     def convmat_nv_shapes(self, packed, rval, lattice, mn, dtype, n1, n2, *, nn=None, mmax=None, nmax=None):
         """Packed vector shapes -> (Exx, Exy, Eyy) [B,N,N], the normal-vector tensor with closed-form [eps] and [1/eps] (include/trx.h:
         trx_convmat_nv_shapes).  rval: [B,S+1] reciprocal values (shapes.ShapeLayer.reciprocal_values); nn: [B,3,n1,n2] float64 products of a

@@ -17,11 +17,12 @@ class rcwa(FieldMixin):
     def __init__(self, freq, order, L, *, dtype=torch.complex64, device=None, stable_eig_grad=True,
                  avoid_Pinv_instability=False, max_Pinv_instability=0.005, precision="high", engine=None, fourier_rule="laurent",
                  nv_sigma=NV_SIGMA_DEFAULT, symmetry=None, symmetry_tol=1e-6, symmetry_grad=False, symmetry_sector=False,
-                 shape_nv_grid=None):
+                 shape_nv_grid=None, shape_nv_grad=False):
         # fourier_rule (extension, keyword-only): "laurent" (the reference's factorisation) or "li" (Li's inverse rule for the in-plane
         # field components of every patterned layer; faster convergence in the order for high-contrast gratings) or "normal"
         # (the normal-vector method for curved / oblique boundaries; field smoothed over nv_sigma grid cells, or add_layer(normal_field=...);
-        # for a ShapeLayer the field of the shape list sampled on shape_nv_grid, an int or (n1, n2))
+        # for a ShapeLayer the field of the shape list sampled on shape_nv_grid, an int or (n1, n2); shape_nv_grad=True (opt-in) keeps that
+        # derived field in the autograd graph, BatchedRCWA)
         # symmetry (extension, keyword-only): None | "x" | "y" | "xy", mirror planes of every patterned layer; the eigenproblem is folded into
         # 2 / 4 independent blocks (BatchedRCWA).  symmetry_residual: per layer the discarded part, or None.
         # symmetry_grad=True (opt-in) lets a differentiable stack use the fold: the eigen-part of the gradient is then the one of the
@@ -35,7 +36,7 @@ class rcwa(FieldMixin):
                               avoid_Pinv_instability=avoid_Pinv_instability, max_Pinv_instability=max_Pinv_instability,
                               precision=precision, engine=engine, fourier_rule=fourier_rule,
                               nv_sigma=nv_sigma, symmetry=symmetry, symmetry_tol=symmetry_tol, symmetry_grad=symmetry_grad,
-                              shape_nv_grid=shape_nv_grid)
+                              shape_nv_grid=shape_nv_grid, shape_nv_grad=shape_nv_grad)
         self._dtype = self._b._dtype
         self._device = self._b._device
         self.freq = torch.as_tensor(freq, dtype=self._dtype, device=self._device)      # rcwa.py:60
