@@ -78,6 +78,47 @@ size_t trx_convmat_li_ws_bytes(int dtype, int batch, int nx, int ny, int ox, int
 int trx_convmat_li(int dtype, int grid_is_complex, const void* grid, int batch, int nx, int ny, int ox, int oy, void* Ex, void* Ey,
                    void* Ux, void* Uy, int* info, void* ws, size_t ws_bytes, void* stream);
 
+/* Li's rule for a list of axis-aligned rectangles in closed form (no grid): kind, voff, S, par, npar as trx_convmat_shapes, every shape a
+ * rectangle (Wx, Wy, Cx, Cy, theta = 0) on the rectangular cell Lx x Ly with the order box (ox, oy) of trx_convmat_li.  rval [batch, S+1]
+ * complex128: rval[b,0] = 1/eps_background, rval[b,s+1] = 1/eps_s - 1/eps_host, so 1/eps = rval_0 + sum_s rval_s chi_s (nesting needs
+ * nothing further; other overlap is the caller's error).  1/eps is piecewise constant along y: between 0 and the y-edges of the rectangles,
+ * reduced into the cell and sorted, lie K = 2S + 1 strips [t_k, t_k+1] of height h_k and midpoint y_k, and
+ *   a_k[p] = rval_0 delta_p0 + sum_{s active in k} rval_s (Wx_s/Lx) sinc(pi p Wx_s/Lx) e^{-2 pi i p Cx_s/Lx},  Uy[k] = Toeplitz(a_k)^-1,
+ *   w_k[q] = (h_k/Ly) sinc(pi q h_k/Ly) e^{-2 pi i q y_k/Ly},   F[m,m',q] = sum_k Uy[k][m,m'] w_k[q],   Ex[(m,n),(m',n')] = F[m,m',n-n'];
+ * Ey is the mirror image (vertical strips between the x-edges, Ux[k] of size (2oy+1)^2, G[n,n',p]).  The strips stand where the grid rows of
+ * trx_convmat_li stand and the weights where its twiddles stand: the inverses, the transform and the scatter are its kernels.
+ * Strip states come from the events: per rectangle lo = (C - W/2) reduced into [0, L), hi = lo + W; hi <= L: it opens at lo and closes at hi
+ * (an edge exactly on the cell boundary stays at L); hi > L: it is active at 0+, closes at hi - L and opens at lo.  Events sort by position,
+ * ties by index (0 the origin, 1 + 2s open, 2 + 2s close); s is active in strip k iff [rank(open) <= k] xor [rank(close) <= k] xor wraps.
+ * A strip of zero height has weight 0 and the state of the one-sided limit.
+ * Outputs: Ex, Ey [batch,N,N] in `dtype`; optional Ux [batch,K,2oy+1,2oy+1], Uy [batch,K,2ox+1,2ox+1] complex128 (NULL: not kept); optional
+ * strip record for the adjoint: brk [batch,2,K+1] fp64 (direction 0: the y-breakpoints t_0 = 0 .. t_K = Ly, direction 1: the x-breakpoints)
+ * and rec [batch,2,3S] int32 (per rectangle: rank of its open event, rank of its close event, wraps).  info[batch] (device): 0 ok; 1 an
+ * rval entry is not finite or rval[b,0] is zero; 2 a Toeplitz block is singular; 3 a
+ * rectangle has theta != 0, a width that is not positive or exceeds the cell, or a centre that is not finite.  All arithmetic is fp64 for both
+ * dtypes: a complex64 call returns the complex128 result rounded once.  One workgroup per (point, direction) stages the list in LDS,
+ * rank-sorts the events (each thread counts what sorts before its own: no data-dependent loop), and writes a_k and w_k summing the active
+ * rectangles in ascending s.  Latency-bound and tiny: K batch Toeplitz blocks where the grid path has (nx + ny) batch.
+ * NOT detected: a rectangle whose medium has 1/eps = 0 (rval_0 + the rval of the rectangle and of its hosts sums to zero, e.g. eps = inf).  The
+ * entry sees sums of rval only and does not know a rectangle's host; above order 0 the Toeplitz block of a function that vanishes on part of
+ * the period is non-singular, so such a layer returns finite numbers with info 0.  The caller keeps eps finite (BatchedRCWA refuses it).
+ * TRX_ERR_ARG: a kind that is not a rectangle (and the list errors of trx_convmat_shapes), Lx or Ly not positive, batch > 65535;
+ * TRX_ERR_UNSUPPORTED: S > 127 (K = 255: one workgroup sorts a point's events), 2*max(ox,oy)+1 > 99 as trx_convmat_li.
+ *
+ * trx_convmat_li_shapes_backward: the adjoint of the strip tables, in PyTorch's convention as trx_convmat_shapes_backward.  ga_x [batch,K,4ox+1]
+ * and gw_y [batch,K,4oy+1]: the adjoints of a_k and w_k of direction 0; ga_y [batch,K,4oy+1], gw_x [batch,K,4ox+1]: of direction 1 (all
+ * complex128).  gpar [batch,npar] fp64 (theta slots and unowned slots 0), grval [batch,S+1] complex128.  d w_(r-1) / d t_r = -d w_r / d t_r =
+ * e^{-2 pi i q t_r/L} / L at the breakpoint of rank r; d t / d C = 1, d t / d W = -+1/2 for the lower / upper edge; d a_k[p] / d Wx = rval_s
+ * cos(pi p Wx/Lx) e^{..} / Lx, d a_k[p] / d Cx = (-2 pi i p/Lx) term.  One workgroup of 256 threads per (point, parameter) and per (point,
+ * value); each thread sums its terms in ascending order, then a fixed tree: no atomics, bit-identical on repetition. */
+size_t trx_convmat_li_shapes_ws_bytes(int dtype, int batch, int S, int ox, int oy);
+int trx_convmat_li_shapes(int dtype, const int* kind, const int* voff, int S, const double* par, int npar, const void* rval, double Lx, double Ly,
+                          int batch, int ox, int oy, void* Ex, void* Ey, void* Ux, void* Uy, double* brk, int* rec, int* info, void* ws,
+                          size_t ws_bytes, void* stream);
+int trx_convmat_li_shapes_backward(const int* kind, const int* voff, int S, const double* par, int npar, const void* rval, double Lx, double Ly,
+                                   int batch, int ox, int oy, const double* brk, const int* rec, const void* ga_x, const void* gw_y,
+                                   const void* ga_y, const void* gw_x, double* gpar, void* grval, void* stream);
+
 /* ---- Fourier factorisation, normal-vector method (no reference counterpart) -----------------------------------------------------------
  * Schuster et al., JOSA A 24, 2880 (2007); Goetz et al., Opt. Express 16, 17295 (2008).  For each grid[b] ([nx, ny], layout and index map as
  * trx_convmat) and an in-plane unit field N normal to the material interfaces:

@@ -25,6 +25,11 @@ _SIGS = {
     "trx_convmat_li_ws_bytes": (c_size_t, [c_int, c_int, c_int, c_int, c_int, c_int]),
     "trx_convmat_li": (c_int, [c_int, c_int, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                c_void_p, c_size_t, c_void_p]),
+    "trx_convmat_li_shapes_ws_bytes": (c_size_t, [c_int, c_int, c_int, c_int, c_int]),
+    "trx_convmat_li_shapes": (c_int, [c_int, c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p, c_double, c_double, c_int, c_int, c_int,
+                                      c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "trx_convmat_li_shapes_backward": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p, c_double, c_double, c_int, c_int, c_int,
+                                               c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "trx_build_pq_aniso": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p,
                                    c_void_p, c_void_p]),
     "trx_build_a_aniso_ws_bytes": (c_size_t, [c_int, c_int, c_int]),

@@ -204,6 +204,67 @@ class ConvMatLiFn(torch.autograd.Function):
         return gg.to(gdt), None, None, None, None
 
 
+def _strip_weights(brk, o, L):
+    """[B, K+1] float64 breakpoints -> [B, K, 4o+1] complex128 strip weights w_k[q] = (h_k/L) sinc(pi q h_k/L) e^{-2 pi i q y_k/L}."""
+    f = ((brk[:, 1:] - brk[:, :-1]) / L)[:, :, None]
+    mid = ((brk[:, 1:] + brk[:, :-1]) / 2)[:, :, None]
+    q = torch.arange(-2 * o, 2 * o + 1, device=brk.device, dtype=torch.float64)[None, None, :]
+    return f * torch.sinc(q * f) * torch.exp(-2j * math.pi * q * mid / L)
+
+
+class ShapeLiFn(torch.autograd.Function):
+    """(Ex, Ey) = Li's inverse-rule matrices of a packed list of axis-aligned rectangles in closed form (include/trx.h:
+    trx_convmat_li_shapes), differentiable in the parameter rows par [B, npar] and the reciprocal values rval [B, S+1].  The backward is
+    ConvMatLiFn's composition with the strips in the place of the grid rows and the strip weights in the place of the twiddles -- the scatter
+    (index_add), gT = -U^H gU U^H per Toeplitz block (batched trx_gemm), the Toeplitz-diagonal sums, and one more small product for the
+    adjoint of the weights, gw_k[q] = sum conj(U_k) gF -- followed by trx_convmat_li_shapes_backward (widths, centres, values; theta gets 0).
+    Once differentiable."""
+
+    @staticmethod
+    def forward(ctx, par, rval, packed, Lx, Ly, ox, oy, cdtype, engine):
+        packed = packed._replace(par=par.detach(), val=packed.val.detach())          # kind, voff and par are read; nothing of the graph is held
+        Ex, Ey, Ux, Uy, brk, rec = engine.convmat_li_shapes(packed, rval, Lx, Ly, ox, oy, cdtype, keep=True)
+        ctx.meta = (packed, Lx, Ly, ox, oy, engine, par.dtype, rval.dtype)
+        ctx.save_for_backward(rval.detach(), Ux, Uy, brk, rec)
+        return Ex, Ey
+
+    @staticmethod
+    def _direction(eng, g, U, wgt, i_scatter, i_diag, n_diag):
+        """g [B, w^2, w'^2] (gE sorted by block entry and by the pair of the other axis), U [B, K, w, w], wgt [B, K, nq2] -> the adjoints
+        (ga [B, K, n_diag], gw [B, K, nq2]) of the Toeplitz rows and of the weights."""
+        B, K, w, _ = U.shape
+        z = torch.complex128
+        gF = torch.zeros((B, w * w, wgt.shape[2]), dtype=z, device=g.device).index_add_(2, i_scatter, g)          # adjoint of the scatter
+        gU = (torch.conj(wgt) @ gF.transpose(1, 2)).reshape(B * K, w, w).contiguous()                             # adjoint of F = sum_k U_k w_k
+        Uf = U.reshape(B * K, w, w)
+        gT = -eng.gemm(eng.gemm(Uf, gU, opA=2), Uf, opB=2)                                                        # -U^H gU U^H
+        ga = torch.zeros((B, K, n_diag), dtype=z, device=g.device).index_add_(2, i_diag, gT.reshape(B, K, w * w))
+        gw = torch.conj(U.reshape(B, K, w * w)) @ gF
+        return ga, gw
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, gEx, gEy):
+        packed, Lx, Ly, ox, oy, eng, pdt, vdt = ctx.meta
+        rval, Ux, Uy, brk, rec = ctx.saved_tensors
+        B, K = Ux.shape[:2]
+        dev, z = Ux.device, torch.complex128
+        wx, wy = 2 * ox + 1, 2 * oy + 1
+        np_, nq = 4 * ox + 1, 4 * oy + 1
+        ix, iy = _diag_index(wx, ox, dev), _diag_index(wy, oy, dev)
+        zeros = lambda n: torch.zeros((B, K, n), dtype=z, device=dev)
+        ga_x, gw_y, ga_y, gw_x = zeros(np_), zeros(nq), zeros(nq), zeros(np_)
+        if gEx is not None:                      # Ex[(m,n),(m',n')] = F[m,m',n-n'],  F = sum over the y-strips of Uy w_y
+            g = gEx.to(z).reshape(B, wx, wy, wx, wy).permute(0, 1, 3, 2, 4).reshape(B, wx * wx, wy * wy)
+            ga_x, gw_y = ShapeLiFn._direction(eng, g, Uy, _strip_weights(brk[:, 0], oy, Ly), iy, ix, np_)
+        if gEy is not None:                      # Ey[(m,n),(m',n')] = G[n,n',m-m'],  G = sum over the x-strips of Ux w_x
+            g = gEy.to(z).reshape(B, wx, wy, wx, wy).permute(0, 2, 4, 1, 3).reshape(B, wy * wy, wx * wx)
+            ga_y, gw_x = ShapeLiFn._direction(eng, g, Ux, _strip_weights(brk[:, 1], ox, Lx), ix, iy, nq)
+        gpar, grval = eng.convmat_li_shapes_backward(packed, rval, Lx, Ly, ox, oy, brk, rec, ga_x, gw_y, ga_y, gw_x)
+        grval = grval if vdt.is_complex else torch.real(grval)
+        return gpar.to(pdt), grval.to(vdt), None, None, None, None, None, None, None
+
+
 class GemmFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, A, B, engine):

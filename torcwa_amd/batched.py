@@ -424,8 +424,22 @@ class BatchedRCWA(FluxMixin, BatchedFieldMixin, VolumeMixin, ReadoutMixin, Secto
         if not isinstance(eps, _shapes.ShapeLayer):
             return
         if self.fourier_rule == "li":
-            raise ValueError('a ShapeLayer needs fourier_rule="laurent" or "normal", got \'li\': the per-row inverses of Li\'s rule are built '
-                             "from grids")
+            # Li's rule has a closed form for axis-aligned rectangles only (trx_convmat_li_shapes): strips of piecewise constant 1/eps
+            names = {_shapes.ELLIPSE: "an ellipse", _shapes.POLYGON: "a polygon"}
+            for i, s in enumerate(eps.shapes):
+                what = names.get(s.kind)
+                if what is None and s.params[4].requires_grad:
+                    what = "a rectangle whose theta requires grad"
+                elif what is None and bool((s.params[4].detach() != 0).any()):
+                    what = "a rotated rectangle"
+                if what is not None:
+                    raise ValueError('a ShapeLayer needs fourier_rule="laurent" or "normal", got \'li\': the per-row inverses of Li\'s rule are built '
+                                     f"from grids, and in closed form only for axis-aligned rectangles (theta identically 0); shape {i} is {what} "
+                                     '-- fourier_rule="normal" takes any shape')
+            for i, t in enumerate([eps.background] + [s.eps for s in eps.shapes]):
+                if not bool(torch.isfinite(t.detach()).all()):      # 1/eps = 0: trx_convmat_li_shapes sees sums of rval only and cannot tell
+                    raise ValueError('a ShapeLayer under fourier_rule="li" needs finite permittivities: '
+                                     f'{"the background" if i == 0 else f"shape {i - 1}"} has a medium with 1/eps = 0')
         if self.symmetry is not None or self.symmetry_sector:
             raise ValueError("a ShapeLayer cannot be combined with symmetry= / symmetry_sector=True: the mirror is detected from grids")
         if self.fourier_rule == "normal" and self.shape_nv_grid is None and normal_field is None:
@@ -474,9 +488,17 @@ class BatchedRCWA(FluxMixin, BatchedFieldMixin, VolumeMixin, ReadoutMixin, Secto
             return C, None, None
 
         def conv_li(v, homog, C):
-            """Li's (Cx, Cy) of a patterned grid; a homogeneous layer has Cx = Cy = C (the scaled identity)."""
+            """Li's (Cx, Cy) of a patterned grid or of a ShapeLayer of axis-aligned rectangles; a homogeneous layer has Cx = Cy = C (the scaled
+            identity)."""
             if homog:
                 return C, C
+            if isinstance(v, _shapes.ShapeLayer):      # axis-aligned rectangles (_refuse_shapes): strips in closed form, no grid
+                packed = v.pack(self._lattice, self.B, self._device)
+                rval = v.reciprocal_values(self.B, self._device)
+                Lx, Ly = float(self._Lxy[0]), float(self._Lxy[1])
+                if diff:
+                    return ag.ShapeLiFn.apply(packed.par, rval, packed, Lx, Ly, self.order[0], self.order[1], cdt, eng)
+                return eng.convmat_li_shapes(packed, rval, Lx, Ly, self.order[0], self.order[1], cdt)
             g = self._grid(v)
             if diff:
                 return ag.ConvMatLiFn.apply(g, self.order[0], self.order[1], cdt, eng)

@@ -15,6 +15,8 @@
 //      over chunks of rows when the caller does not keep U (the chunk bounds the workspace);
 //   4. scatter of F, G into E_x, E_y [B,N,N] in the compute dtype.
 #include <algorithm>
+#include <cmath>
+#include <vector>
 
 #include "common.hpp"
 
@@ -226,8 +228,9 @@ LiLayout li_layout(int batch, int nx, int ny, int ox, int oy) {
 }
 
 // One direction: coef [B, nrows, 4o+1] -> Toeplitz inverses (w = 2o+1) per row -> Out[b] = sum_r U_r^T Wtw[r, :]  ([w^2, 4o'+1]).
-int li_direction(hipStream_t s, const zc* coef, int nrows, int w, const zc* Wtw, int nq2, int batch, zc* Ukeep, zc* Uws, int rc, zc* Out,
-                 int* info) {
+// Wtw: [nrows, nq2] shared by the batch (w_bstride = 0: the twiddles of a grid) or one table per point (the strip weights of a shape list).
+int li_direction(hipStream_t s, const zc* coef, int nrows, int w, const zc* Wtw, long w_bstride, int nq2, int batch, zc* Ukeep, zc* Uws, int rc,
+                 zc* Out, int* info) {
     const long ww = (long)w * w;
     const size_t lds = toeplitz_lds_bytes(w);
     if (set_max_dyn_smem((const void*)toeplitz_inv_kernel, lds)) return TRX_ERR_LAUNCH;
@@ -235,15 +238,15 @@ int li_direction(hipStream_t s, const zc* coef, int nrows, int w, const zc* Wtw,
     if (Ukeep) {                     // the caller keeps every inverse (adjoint): one pass, U in place
         TRX_LAUNCH(toeplitz_inv_kernel, dim3(nrows, batch), dim3(256), lds, s, coef, nrows, 0, w, Ukeep, (long)nrows * ww, info);
         TRX_CHECK_LAUNCH();
-        return gemm<double>(s, TRX_OP_T, TRX_OP_N, (int)ww, nq2, nrows, one, Ukeep, (int)ww, (long)nrows * ww, Wtw, nq2, 0, zero, Out, nq2,
-                            ww * nq2, batch);
+        return gemm<double>(s, TRX_OP_T, TRX_OP_N, (int)ww, nq2, nrows, one, Ukeep, (int)ww, (long)nrows * ww, Wtw, nq2, w_bstride, zero, Out,
+                            nq2, ww * nq2, batch);
     }
     for (int r0 = 0; r0 < nrows; r0 += rc) {
         const int rn = std::min(rc, nrows - r0);
         TRX_LAUNCH(toeplitz_inv_kernel, dim3(rn, batch), dim3(256), lds, s, coef, nrows, r0, w, Uws, (long)rn * ww, info);
         TRX_CHECK_LAUNCH();
-        int rc2 = gemm<double>(s, TRX_OP_T, TRX_OP_N, (int)ww, nq2, rn, one, Uws, (int)ww, (long)rn * ww, Wtw + (long)r0 * nq2, nq2, 0,
-                               r0 == 0 ? zero : one, Out, nq2, ww * nq2, batch);
+        int rc2 = gemm<double>(s, TRX_OP_T, TRX_OP_N, (int)ww, nq2, rn, one, Uws, (int)ww, (long)rn * ww, Wtw + (long)r0 * nq2, nq2,
+                               w_bstride, r0 == 0 ? zero : one, Out, nq2, ww * nq2, batch);
         if (rc2) return rc2;
     }
     return TRX_OK;
@@ -274,10 +277,283 @@ int convmat_li_t(int cplx, const void* grid, int batch, int nx, int ny, int ox, 
     TRX_LAUNCH(twiddle_kernel, dim3(cdiv_i((long)nx * np, 256)), dim3(256), 0, s, nx, ox, twx);
     TRX_CHECK_LAUNCH();
     // E_x: inverses of the x-Toeplitz blocks per grid row y, transformed along y
-    int rc = li_direction(s, ay, ny, wx, twy, nq, batch, (zc*)Uy, Uw, L.rc_y, F, info);
+    int rc = li_direction(s, ay, ny, wx, twy, 0, nq, batch, (zc*)Uy, Uw, L.rc_y, F, info);
     if (rc) return rc;
     // E_y: inverses of the y-Toeplitz blocks per grid row x, transformed along x
-    rc = li_direction(s, ax, nx, wy, twx, np, batch, (zc*)Ux, Uw, L.rc_x, G, info);
+    rc = li_direction(s, ax, nx, wy, twx, 0, np, batch, (zc*)Ux, Uw, L.rc_x, G, info);
+    if (rc) return rc;
+    TRX_LAUNCH((li_scatter_kernel<T>), dim3(cdiv_i(N, 256), N, batch), dim3(256), 0, s, (const zc*)F, (const zc*)G, ox, oy, (cx<T>*)Ex,
+               (cx<T>*)Ey);
+    TRX_CHECK_LAUNCH();
+    return TRX_OK;
+}
+
+// ---- Li's rule for a list of axis-aligned rectangles, in closed form ---------------------------------------------------------------------
+// 1/eps = rval[0] + sum_s rval[s+1] chi_s is piecewise constant along y: the cell splits into K = 2S + 1 horizontal strips between 0 and the
+// y-edges of the rectangles.  In strip k the x-coefficients of 1/eps are a_k[p] = rval[0] delta_p0 + sum_{s active in k} rval[s+1] (Wx/Lx)
+// sinc(pi p Wx/Lx) e^{-2 pi i p Cx/Lx}, and the y-transform of the strip's indicator is w_k[q] = (h_k/Ly) sinc(pi q h_k/Ly) e^{-2 pi i q y_k/Ly}:
+// the strips stand where the grid rows of trx_convmat_li stand and the weights where its twiddles stand.  E_y: the same with x and y exchanged.
+// Direction d = 0: strips along y, coefficients along x (E_x);  d = 1: the mirror image (E_y).
+//
+// Events of one direction: index 0 the origin, 1 + 2s the lower edge of rectangle s (it opens), 2 + 2s its upper edge (it closes), each
+// reduced into the cell; a rectangle that crosses the cell boundary is active at 0+ (wraps = 1) and closes before it opens.  Each thread
+// counts the events that sort before its own (ties by index): a rank sort without a data-dependent loop.  Rectangle s is active in strip k
+// iff [rank(open) <= k] xor [rank(close) <= k] xor wraps: a strip of zero height carries weight 0 and the state of the one-sided limit.
+constexpr int LS_BLOCK = 256;
+constexpr int LS_SMAX = 127;                       // K = 2S + 1 <= 255 events: one workgroup sorts a point's events
+
+__device__ __forceinline__ bool finite_d(double v) { return fabs(v) <= 1.7976931348623157e308; }
+__device__ __forceinline__ double sincpi_f(double x) {           // sin(pi x) / (pi x)
+    if (x == 0.0) return 1.0;
+    double s, c;
+    sincospi(x, &s, &c);
+    return s / (M_PI * x);
+}
+__device__ __forceinline__ zc expm2pi(double x) {                // e^{-2 pi i x}
+    double s, c;
+    sincospi(-2.0 * x, &s, &c);
+    return zc(c, s);
+}
+__device__ __forceinline__ bool strip_active(const int* rk, int s, int k) { return ((rk[3 * s] <= k) != (rk[3 * s + 1] <= k)) != (rk[3 * s + 2] != 0); }
+
+// grid (2, batch).  coef[d]: [B, K, 4 o_c + 1] (the rows of toeplitz_inv_kernel), wgt[d]: [B, K, 4 o_s + 1] with o_c / o_s the order along the
+// coefficient / strip axis of direction d.  brk [B, 2, K + 1] and rec [B, 2, 3 S] (rank of open, rank of close, wraps) may be NULL.
+__global__ __launch_bounds__(LS_BLOCK) void li_strips_kernel(const int* __restrict__ voff, int S, const double* __restrict__ par, int npar,
+                                                             const zc* __restrict__ rval, double Lx, double Ly, int ox, int oy,
+                                                             zc* __restrict__ coef0, zc* __restrict__ coef1, zc* __restrict__ wgt0,
+                                                             zc* __restrict__ wgt1, double* __restrict__ brk, int* __restrict__ rec,
+                                                             int* __restrict__ info) {
+    __shared__ double pos[2 * LS_SMAX + 2], srt[2 * LS_SMAX + 2], cw[LS_SMAX], cc[LS_SMAX];
+    __shared__ zc rv[LS_SMAX];
+    __shared__ int rk[3 * LS_SMAX], flag[2];
+    const int d = blockIdx.x, b = blockIdx.y, tid = threadIdx.x;
+    const int K = 2 * S + 1;
+    const double Ls = d == 0 ? Ly : Lx, Lc = d == 0 ? Lx : Ly;   // period along the strip axis / the coefficient axis
+    const int oc = d == 0 ? ox : oy, os = d == 0 ? oy : ox;
+    const int nc = 4 * oc + 1, nw = 4 * os + 1;
+    const double* pr = par + (long)b * npar;
+    const zc* rvb = rval + (long)b * (S + 1);
+    if (tid == 0) { flag[0] = 0; flag[1] = 0; pos[0] = 0.0; }
+    if (tid <= K) srt[tid] = tid == K ? Ls : 0.0;
+    __syncthreads();
+    if (tid < S) {
+        const double* q = pr + voff[tid];
+        const double ws = q[d == 0 ? 1 : 0], cs = q[d == 0 ? 3 : 2];
+        cw[tid] = q[d == 0 ? 0 : 1];
+        cc[tid] = q[d == 0 ? 2 : 3];
+        const zc r = rvb[tid + 1];
+        rv[tid] = r;
+        double lo = cs - 0.5 * ws;
+        lo -= floor(lo / Ls) * Ls;
+        if (lo >= Ls) lo -= Ls;                    // a tiny negative edge rounds to the period itself
+        if (lo < 0.0) lo = 0.0;
+        const double hi = lo + ws;
+        const int wraps = hi > Ls;                 // an edge exactly on the cell boundary stays at Ls
+        pos[1 + 2 * tid] = lo;
+        pos[2 + 2 * tid] = wraps ? hi - Ls : hi;
+        rk[3 * tid + 2] = wraps;
+        if (!finite_d(r.x) || !finite_d(r.y)) flag[0] = 1;        // benign race: every writer stores the same 1
+        if (!(q[4] == 0.0) || !(q[0] > 0.0) || !(q[1] > 0.0) || !(q[0] <= Lx) || !(q[1] <= Ly) || !finite_d(q[2]) || !finite_d(q[3])) flag[1] = 1;
+    }
+    if (tid == S) {
+        const zc r = rvb[0];
+        if (!finite_d(r.x) || !finite_d(r.y) || (r.x == 0.0 && r.y == 0.0)) flag[0] = 1;
+    }
+    __syncthreads();
+    if (tid < K) {
+        const double mine = pos[tid];
+        int r = 0;
+        for (int e = 0; e < K; ++e) {
+            const double o = pos[e];
+            r += (o < mine || (o == mine && e < tid)) ? 1 : 0;
+        }
+        srt[r] = mine;
+        if (tid > 0) rk[3 * ((tid - 1) >> 1) + ((tid - 1) & 1)] = r;
+    }
+    __syncthreads();
+    zc* a = (d == 0 ? coef0 : coef1) + (long)b * K * nc;
+    for (int e = tid; e < K * nc; e += LS_BLOCK) {
+        const int k = e / nc, p = e - k * nc - 2 * oc;
+        zc acc = p == 0 ? rvb[0] : zc(0.0, 0.0);
+        for (int s = 0; s < S; ++s) {
+            if (!strip_active(rk, s, k)) continue;
+            const double f = cw[s] / Lc;
+            cfma(acc, rv[s], (f * sincpi_f(p * f)) * expm2pi(p * cc[s] / Lc));
+        }
+        a[e] = acc;
+    }
+    zc* wg = (d == 0 ? wgt0 : wgt1) + (long)b * K * nw;
+    for (int e = tid; e < K * nw; e += LS_BLOCK) {
+        const int k = e / nw, q = e - k * nw - 2 * os;
+        const double f = (srt[k + 1] - srt[k]) / Ls, mid = 0.5 * (srt[k] + srt[k + 1]);
+        wg[e] = (f * sincpi_f(q * f)) * expm2pi(q * mid / Ls);
+    }
+    if (brk && tid <= K) brk[((long)b * 2 + d) * (K + 1) + tid] = srt[tid];
+    if (rec)
+        for (int e = tid; e < 3 * S; e += LS_BLOCK) rec[((long)b * 2 + d) * 3 * S + e] = rk[e];
+    if (d == 0 && tid == 0) {                      // both directions see the same list: one of them reports
+        const int code = flag[1] ? 3 : flag[0] ? 1 : 0;
+        if (code) info[b] = code;
+    }
+}
+
+__device__ __forceinline__ zc ls_block_sum(zc v, zc* red) {
+    red[threadIdx.x] = v;
+    __syncthreads();
+    for (int h = LS_BLOCK / 2; h > 0; h >>= 1) {
+        if ((int)threadIdx.x < h) red[threadIdx.x] += red[threadIdx.x + h];
+        __syncthreads();
+    }
+    return red[0];
+}
+
+// Adjoint of li_strips_kernel.  grid (npar + S + 1, batch): item w < npar is par[b, w], w = npar is rval[b, 0], w = npar + 1 + s is
+// rval[b, s + 1].  ga[d] / gw[d]: the adjoints of coef[d] / wgt[d].  A width or centre along axis c gets the coefficient part from the
+// direction whose coefficients run along c (d = c) and the breakpoint part from the other one: with w_k[q] = (1/L) int_strip e^{-2 pi i q t/L} dt,
+// d w_{r-1} / d t_r = -d w_r / d t_r = e^{-2 pi i q t_r / L} / L at the breakpoint of rank r.
+__global__ __launch_bounds__(LS_BLOCK) void li_strips_backward_kernel(const int* __restrict__ voff, int S, const double* __restrict__ par, int npar,
+                                                                      const zc* __restrict__ rval, double Lx, double Ly, int ox, int oy,
+                                                                      const double* __restrict__ brk, const int* __restrict__ rec,
+                                                                      const zc* __restrict__ ga0, const zc* __restrict__ gw0,
+                                                                      const zc* __restrict__ ga1, const zc* __restrict__ gw1,
+                                                                      double* __restrict__ gpar, zc* __restrict__ grval) {
+    __shared__ zc red[LS_BLOCK];
+    const int w = blockIdx.x, b = blockIdx.y, tid = threadIdx.x;
+    const int K = 2 * S + 1;
+    const double* pr = par + (long)b * npar;
+    zc acc(0.0, 0.0);
+    if (w >= npar) {                               // a value: grval = sum conj(d a / d rval) ga over both directions
+        const int s = w - npar - 1;
+        for (int d = 0; d < 2; ++d) {
+            const int oc = d == 0 ? ox : oy, nc = 4 * oc + 1;
+            const zc* ga = (d == 0 ? ga0 : ga1) + (long)b * K * nc;
+            const int* rk = rec + ((long)b * 2 + d) * 3 * S;
+            if (s < 0) {
+                for (int k = tid; k < K; k += LS_BLOCK) acc += ga[k * nc + 2 * oc];
+                continue;
+            }
+            const double* q = pr + voff[s];
+            const double Lc = d == 0 ? Lx : Ly, f = q[d] / Lc, c = q[2 + d];
+            for (int e = tid; e < K * nc; e += LS_BLOCK) {
+                const int k = e / nc, p = e - k * nc - 2 * oc;
+                if (!strip_active(rk, s, k)) continue;
+                cfma_conj(acc, (f * sincpi_f(p * f)) * expm2pi(p * c / Lc), ga[e]);
+            }
+        }
+        const zc tot = ls_block_sum(acc, red);
+        if (tid == 0) grval[(long)b * (S + 1) + s + 1] = tot;
+        return;
+    }
+    int s = -1;
+    for (int t = 0; t < S; ++t)
+        if (w >= voff[t] && w < voff[t + 1]) s = t;
+    const int j = s < 0 ? 4 : w - voff[s];
+    if (j >= 4) {                                  // theta, or a slot of the row that belongs to no shape
+        if (tid == 0) gpar[(long)b * npar + w] = 0.0;
+        return;
+    }
+    const int c = j & 1;                           // the axis the parameter lies along; j < 2: a width, else a centre
+    const bool width = j < 2;
+    const int o = c == 0 ? ox : oy, n = 4 * o + 1;
+    const double L = c == 0 ? Lx : Ly;
+    const double* q = pr + voff[s];
+    const zc delta = rval[(long)b * (S + 1) + s + 1];
+    {                                              // coefficients along c: direction c
+        const zc* ga = (c == 0 ? ga0 : ga1) + (long)b * K * n;
+        const int* rk = rec + ((long)b * 2 + c) * 3 * S;
+        const double f = q[c] / L, ctr = q[2 + c];
+        for (int e = tid; e < K * n; e += LS_BLOCK) {
+            const int k = e / n, p = e - k * n - 2 * o;
+            if (!strip_active(rk, s, k)) continue;
+            const zc ph = expm2pi(p * ctr / L);
+            zc dv;
+            if (width) {
+                double sn, cs;
+                sincospi(p * f, &sn, &cs);
+                dv = (cs / L) * ph;                // d(W/L sinc(pi p W/L)) / dW = cos(pi p W/L) / L
+            } else {
+                const zc v = (f * sincpi_f(p * f)) * ph;
+                const double g = 2.0 * M_PI * p / L;
+                dv = zc(g * v.y, -g * v.x);        // -2 pi i p / L times the term
+            }
+            dv = delta * dv;
+            acc.x += ga[e].x * dv.x + ga[e].y * dv.y;            // Re(conj(ga) d a / d par)
+        }
+    }
+    {                                              // breakpoints along c: the other direction
+        const int d = 1 - c;
+        const zc* gw = (d == 0 ? gw0 : gw1) + (long)b * K * n;
+        const int* rk = rec + ((long)b * 2 + d) * 3 * S;
+        const double* t = brk + ((long)b * 2 + d) * (K + 1);
+        for (int e = tid; e < 2 * n; e += LS_BLOCK) {
+            const int edge = e / n, qq = e - edge * n - 2 * o;
+            int r = rk[3 * s + edge];              // 1 .. 2S: the strips r - 1 and r meet at this breakpoint
+            r = r < 1 ? 1 : r > 2 * S ? 2 * S : r; // (a record of a refused point stays inside the tables)
+            const double sign = !width ? 1.0 : edge == 0 ? -0.5 : 0.5;
+            const zc ph = expm2pi(qq * t[r] / L);
+            const zc g = gw[(r - 1) * n + qq + 2 * o] - gw[r * n + qq + 2 * o];
+            acc.x += sign / L * (g.x * ph.x + g.y * ph.y);
+        }
+    }
+    const zc tot = ls_block_sum(acc, red);
+    if (tid == 0) gpar[(long)b * npar + w] = tot.x;
+}
+
+struct LiShapesLayout {              // workspace carving of trx_convmat_li_shapes (element counts of zc)
+    long coef0, coef1, wgt0, wgt1, F, G, U;
+    int rc0, rc1;                    // strips per chunk of the Toeplitz inverses when U is not an output
+};
+
+LiShapesLayout li_shapes_layout(int batch, int S, int ox, int oy) {
+    LiShapesLayout L;
+    const long K = 2 * S + 1, wx = 2 * ox + 1, wy = 2 * oy + 1, np = 4 * ox + 1, nq = 4 * oy + 1, N = wx * wy;
+    L.coef0 = L.wgt1 = (long)batch * K * np;
+    L.coef1 = L.wgt0 = (long)batch * K * nq;
+    L.F = (long)batch * wx * wx * nq;
+    L.G = (long)batch * wy * wy * np;
+    const long cap = N * N / 2;      // as li_layout: the same chunks for both dtypes
+    L.rc0 = (int)std::max(1L, std::min(K, cap / (wx * wx)));
+    L.rc1 = (int)std::max(1L, std::min(K, cap / (wy * wy)));
+    L.U = (long)batch * std::max((long)L.rc0 * wx * wx, (long)L.rc1 * wy * wy);
+    return L;
+}
+
+// kind / voff of a list of rectangles, checked on the host (one copy and one synchronisation of s): the check of trx_convmat_shapes, and
+// nothing but rectangles
+int rectangles_check(hipStream_t s, const int* kind, const int* voff, int S, int npar) {
+    std::vector<int> h((size_t)2 * S + 1);
+    if (hipMemcpyAsync(h.data(), kind, sizeof(int) * S, hipMemcpyDeviceToHost, s) != hipSuccess) return TRX_ERR_LAUNCH;
+    if (hipMemcpyAsync(h.data() + S, voff, sizeof(int) * (S + 1), hipMemcpyDeviceToHost, s) != hipSuccess) return TRX_ERR_LAUNCH;
+    if (hipStreamSynchronize(s) != hipSuccess) return TRX_ERR_LAUNCH;
+    const int* vo = h.data() + S;
+    if (vo[0] < 0 || vo[S] > npar) return TRX_ERR_ARG;
+    for (int i = 0; i < S; ++i)
+        if (h[i] != 1 || vo[i + 1] - vo[i] != 5) return TRX_ERR_ARG;
+    return TRX_OK;
+}
+
+inline bool good_period(double L) { return L > 0.0 && std::isfinite(L); }
+
+template <class T>
+int convmat_li_shapes_t(const int* voff, int S, const double* par, int npar, const void* rval, double Lx, double Ly, int batch, int ox, int oy,
+                        void* Ex, void* Ey, void* Ux, void* Uy, double* brk, int* rec, int* info, void* ws, hipStream_t s) {
+    const LiShapesLayout L = li_shapes_layout(batch, S, ox, oy);
+    zc* coef0 = reinterpret_cast<zc*>(ws);
+    zc* coef1 = coef0 + L.coef0;
+    zc* wgt0 = coef1 + L.coef1;
+    zc* wgt1 = wgt0 + L.wgt0;
+    zc* F = wgt1 + L.wgt1;
+    zc* G = F + L.F;
+    zc* Uw = G + L.G;
+    const int K = 2 * S + 1, wx = 2 * ox + 1, wy = 2 * oy + 1, np = 4 * ox + 1, nq = 4 * oy + 1, N = wx * wy;
+    if (hipMemsetAsync(info, 0, sizeof(int) * (size_t)batch, s) != hipSuccess) return TRX_ERR_LAUNCH;
+    TRX_LAUNCH(li_strips_kernel, dim3(2, batch), dim3(LS_BLOCK), 0, s, voff, S, par, npar, (const zc*)rval, Lx, Ly, ox, oy, coef0, coef1, wgt0, wgt1,
+               brk, rec, info);
+    TRX_CHECK_LAUNCH();
+    // E_x: inverses of the x-Toeplitz blocks per horizontal strip, weighted along y;  E_y: the mirror image
+    int rc = li_direction(s, coef0, K, wx, wgt0, (long)K * nq, nq, batch, (zc*)Uy, Uw, L.rc0, F, info);
+    if (rc) return rc;
+    rc = li_direction(s, coef1, K, wy, wgt1, (long)K * np, np, batch, (zc*)Ux, Uw, L.rc1, G, info);
     if (rc) return rc;
     TRX_LAUNCH((li_scatter_kernel<T>), dim3(cdiv_i(N, 256), N, batch), dim3(256), 0, s, (const zc*)F, (const zc*)G, ox, oy, (cx<T>*)Ex,
                (cx<T>*)Ey);
@@ -308,4 +584,43 @@ extern "C" int trx_convmat_li(int dtype, int grid_is_complex, const void* grid, 
     hipStream_t s = trx::api_stream(stream);
     if (dtype == TRX_C64) return convmat_li_t<float>(grid_is_complex, grid, batch, nx, ny, ox, oy, Ex, Ey, Ux, Uy, info, ws, s);
     return convmat_li_t<double>(grid_is_complex, grid, batch, nx, ny, ox, oy, Ex, Ey, Ux, Uy, info, ws, s);
+}
+
+extern "C" size_t trx_convmat_li_shapes_ws_bytes(int dtype, int batch, int S, int ox, int oy) {
+    (void)dtype;                     // every buffer is complex128 and the strip chunk is the same for both dtypes
+    if (batch <= 0 || S <= 0 || ox < 0 || oy < 0) return 0;
+    const LiShapesLayout L = li_shapes_layout(batch, S, ox, oy);
+    return sizeof(zc) * (size_t)(L.coef0 + L.coef1 + L.wgt0 + L.wgt1 + L.F + L.G + L.U);
+}
+
+extern "C" int trx_convmat_li_shapes(int dtype, const int* kind, const int* voff, int S, const double* par, int npar, const void* rval, double Lx,
+                                     double Ly, int batch, int ox, int oy, void* Ex, void* Ey, void* Ux, void* Uy, double* brk, int* rec, int* info,
+                                     void* ws, size_t ws_bytes, void* stream) {
+    if (!kind || !voff || !par || !rval || !Ex || !Ey || !info || !ws) return TRX_ERR_ARG;
+    if (S <= 0 || npar <= 0 || batch <= 0 || batch > 65535 || ox < 0 || oy < 0 || !good_period(Lx) || !good_period(Ly)) return TRX_ERR_ARG;
+    if (dtype != TRX_C64 && dtype != TRX_C128) return TRX_ERR_DTYPE;
+    if (S > LS_SMAX) return TRX_ERR_UNSUPPORTED;
+    if (toeplitz_lds_bytes(2 * (ox > oy ? ox : oy) + 1) > LI_LDS_MAX) return TRX_ERR_UNSUPPORTED;      // 2o+1 <= 99, as trx_convmat_li
+    if (ws_bytes < trx_convmat_li_shapes_ws_bytes(dtype, batch, S, ox, oy)) return TRX_ERR_WORKSPACE;
+    hipStream_t s = trx::api_stream(stream);
+    const int rc = rectangles_check(s, kind, voff, S, npar);
+    if (rc) return rc;
+    if (dtype == TRX_C64)
+        return convmat_li_shapes_t<float>(voff, S, par, npar, rval, Lx, Ly, batch, ox, oy, Ex, Ey, Ux, Uy, brk, rec, info, ws, s);
+    return convmat_li_shapes_t<double>(voff, S, par, npar, rval, Lx, Ly, batch, ox, oy, Ex, Ey, Ux, Uy, brk, rec, info, ws, s);
+}
+
+extern "C" int trx_convmat_li_shapes_backward(const int* kind, const int* voff, int S, const double* par, int npar, const void* rval, double Lx,
+                                              double Ly, int batch, int ox, int oy, const double* brk, const int* rec, const void* ga_x,
+                                              const void* gw_y, const void* ga_y, const void* gw_x, double* gpar, void* grval, void* stream) {
+    if (!kind || !voff || !par || !rval || !brk || !rec || !ga_x || !gw_y || !ga_y || !gw_x || !gpar || !grval) return TRX_ERR_ARG;
+    if (S <= 0 || npar <= 0 || batch <= 0 || batch > 65535 || ox < 0 || oy < 0 || !good_period(Lx) || !good_period(Ly)) return TRX_ERR_ARG;
+    if (S > LS_SMAX || npar + S + 1 > 65535) return TRX_ERR_UNSUPPORTED;
+    hipStream_t s = trx::api_stream(stream);
+    const int rc = rectangles_check(s, kind, voff, S, npar);
+    if (rc) return rc;
+    TRX_LAUNCH(li_strips_backward_kernel, dim3(npar + S + 1, batch), dim3(LS_BLOCK), 0, s, voff, S, par, npar, (const zc*)rval, Lx, Ly, ox, oy, brk,
+               rec, (const zc*)ga_x, (const zc*)gw_y, (const zc*)ga_y, (const zc*)gw_x, gpar, (zc*)grval);
+    TRX_CHECK_LAUNCH();
+    return TRX_OK;
 }

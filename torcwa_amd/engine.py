@@ -236,6 +236,51 @@ class Engine:
         return Ex, Ey, Ux, Uy
 
     @_phase("assembly (convolution matrices, E^-1, A = PQ)")
+    def convmat_li_shapes(self, packed, rval, Lx, Ly, ox, oy, dtype, keep=False):
+        """Packed axis-aligned rectangles -> (Ex, Ey) [B,N,N], Li's inverse-rule matrices in closed form (include/trx.h:
+        trx_convmat_li_shapes).  rval: [B,S+1] reciprocal values (shapes.ShapeLayer.reciprocal_values).  keep: also return what the adjoint
+        needs, (Ex, Ey, Ux [B,K,2oy+1,2oy+1], Uy [B,K,2ox+1,2ox+1], brk [B,2,K+1] float64, rec [B,2,3S] int32), K = 2S + 1."""
+        kind, voff, par, _, _ = self._shape_args(packed)
+        rval = self._c(rval.detach().to(device=self.device, dtype=torch.complex128))
+        B, npar = par.shape
+        S = int(kind.numel())
+        K = 2 * S + 1
+        N = (2 * ox + 1) * (2 * oy + 1)
+        Ex = torch.empty((B, N, N), dtype=dtype, device=self.device)
+        Ey = torch.empty_like(Ex)
+        Ux = Uy = brk = rec = None
+        if keep:
+            Ux = torch.empty((B, K, 2 * oy + 1, 2 * oy + 1), dtype=torch.complex128, device=self.device)
+            Uy = torch.empty((B, K, 2 * ox + 1, 2 * ox + 1), dtype=torch.complex128, device=self.device)
+            brk = torch.empty((B, 2, K + 1), dtype=torch.float64, device=self.device)
+            rec = torch.empty((B, 2, 3 * S), dtype=torch.int32, device=self.device)
+        info = self._ints(B)
+        nws = self.lib.convmat_li_shapes_ws_bytes(_CODE[dtype], B, S, ox, oy)
+        ws = self._ws(nws)
+        opt = lambda t: t.data_ptr() if t is not None else None
+        self.lib.check(self.lib.convmat_li_shapes(_CODE[dtype], kind.data_ptr(), voff.data_ptr(), S, par.data_ptr(), npar, rval.data_ptr(),
+                                                  float(Lx), float(Ly), B, ox, oy, Ex.data_ptr(), Ey.data_ptr(), opt(Ux), opt(Uy), opt(brk),
+                                                  opt(rec), info.data_ptr(), ws.data_ptr(), nws, self.stream))
+        self._info(info, "convmat_li_shapes (1: an rval entry not finite or a zero background value, 2: singular Toeplitz block, 3: a rectangle that is "
+                         "rotated, without area or wider than the cell)")
+        return (Ex, Ey, Ux, Uy, brk, rec) if keep else (Ex, Ey)
+
+    @_phase("assembly (convolution matrices, E^-1, A = PQ)")
+    def convmat_li_shapes_backward(self, packed, rval, Lx, Ly, ox, oy, brk, rec, ga_x, gw_y, ga_y, gw_x):
+        """(gpar [B, npar] fp64, grval [B, S+1] complex128) from the adjoints of the strip tables (trx_convmat_li_shapes_backward)."""
+        kind, voff, par, _, _ = self._shape_args(packed)
+        rval = self._c(rval.detach().to(device=self.device, dtype=torch.complex128))
+        B, npar = par.shape
+        S = int(kind.numel())
+        tabs = [self._c(t.to(torch.complex128)) for t in (ga_x, gw_y, ga_y, gw_x)]
+        gpar = torch.empty((B, npar), dtype=torch.float64, device=self.device)
+        grval = torch.empty((B, S + 1), dtype=torch.complex128, device=self.device)
+        self.lib.check(self.lib.convmat_li_shapes_backward(kind.data_ptr(), voff.data_ptr(), S, par.data_ptr(), npar, rval.data_ptr(), float(Lx),
+                                                           float(Ly), B, ox, oy, self._c(brk).data_ptr(), self._c(rec).data_ptr(),
+                                                           *[t.data_ptr() for t in tabs], gpar.data_ptr(), grval.data_ptr(), self.stream))
+        return gpar, grval
+
+    @_phase("assembly (convolution matrices, E^-1, A = PQ)")
     def normal_field(self, grid, sigma, hx=1.0, hy=1.0):
         """[B,nx,ny] grid -> [B,3,nx,ny] float64 products (Nx^2, Nx Ny, Ny^2) of the normal-vector field derived from the grid
         (include/trx.h: trx_normal_field; sigma in cells, hx / hy the grid spacings)."""
